@@ -29,6 +29,12 @@ The cpu_baseline leg times the CPU oracle (oracle/kp_oracle.c, a C restatement o
 reference's DP) on a bounded sample of the same counts: the reference's own fan-out
 (README.md:39-51, one process per grid point) as one single-threaded oracle task per
 (alpha, c) on every host core, and one task alone on one core.
+
+A run without ``--full`` does only what the headline figure needs: set-up, warm-up, the
+timed steps, the result line.  ``--full`` adds the legs that take runs of their own: the
+full grid CV wall-clock with its modelled 2/4/8-GPU jobs (cv_full_grid, scaling_by_gpus)
+and the cpu_baseline leg.  ``--dump-outputs DIR`` writes what the last timed step returned
+(dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -382,6 +388,27 @@ class Shadows:
             p.wait(timeout=60)
 
 
+DUMP_CELLS = 1 << 18  # lattice cells sampled per lane by --dump-outputs (1 MiB of float32)
+
+
+def dump_outputs(dirname, plan, groups, out):
+    """``--dump-outputs``: what the last timed step computed, as ``DIR/<name>.npy``.
+    root_train, root_test (float32 [lanes]) and n_leaves (float64 [lanes], the uint64
+    counts) are the arrays Plan.run returned for the pass ``groups``; cell_scores (float32
+    [lanes, DUMP_CELLS]) are the pass's train scores, still resident on the device, at a
+    fixed seeded sample of lattice cells (cell_index, float64: the indices are below 2^53);
+    lane_params (float64 [lanes, 4]) names each lane's fold, alpha, beta and penalty."""
+    rt, re, nlv = out
+    os.makedirs(dirname, exist_ok=True)
+    cells = np.sort(np.random.RandomState(17).randint(0, plan.info["npat"], size=DUMP_CELLS, dtype=np.int64))
+    scores = np.stack([plan.gather_cells(lane, cells.astype(np.uint64)) for lane in range(len(rt))])
+    params = np.array([[f, a, b, c] for f, a, b, pens in groups for c in pens], np.float64)
+    for name, arr in (("root_train", rt.astype(np.float32)), ("root_test", re.astype(np.float32)),
+                      ("n_leaves", nlv.astype(np.float64)), ("cell_index", cells.astype(np.float64)),
+                      ("cell_scores", scores.astype(np.float32)), ("lane_params", params)):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def note(msg):
     """A progress line on stderr (the JSON line is stdout's only content)."""
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
@@ -488,17 +515,26 @@ def main():
     ap.add_argument("--config", default="9mer", choices=sorted(CONFIGS),
                     help="9mer = BASELINE configs[3] (the headline); 11mer = configs[4] (super-pattern restricted)")
     ap.add_argument("--pattern", default=None, help="override the config's general pattern")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the full grid CV wall-clock with its "
+                         "modelled multi-GPU jobs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="host cores for the CPU baseline (default: this job's CPU share, host_cores())")
     ap.add_argument("--max-block", type=int, default=0)
-    ap.add_argument("--no-full-cv", action="store_true", help="skip the full grid CV wall-clock leg")
+    ap.add_argument("--no-full-cv", action="store_true", help="with --full: skip the full grid CV wall-clock leg")
     ap.add_argument("--model-worlds", default="2,4,8",
                     help="GPU counts whose full-CV wall-clock is modelled at N=1 (comma list, empty = none)")
     ap.add_argument("--shadow", action="store_true", help=argparse.SUPPRESS)  # a modelled rank's host side
     a = ap.parse_args()
     if a.shadow:
         return shadow_main(a.config, a.pattern or CONFIGS[a.config]["gen_pat"])
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    run_cv = a.full and not a.no_full_cv
+    run_cpu = a.full and not a.no_cpu_baseline
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -541,7 +577,7 @@ def main():
     # 5 of a fold's 49 (alpha, c) lanes, some spanning two alphas)
     step_passes = engine.plan_passes(groups, cap, width)[0]
     model_worlds = tuple(int(x) for x in a.model_worlds.split(",") if x.strip())
-    worlds = () if a.no_full_cv else ((world,) + model_worlds if world == 1 else (world,))
+    worlds = () if not run_cv else ((world,) + model_worlds if world == 1 else (world,))
     most = max([sum(len(g[3]) for g in p) for p in step_passes] +
                [sum(len(g[3]) for g in p) for w in worlds for passes in cv_shares(prep, w, cap, width) for p in passes])
     t0 = time.perf_counter()
@@ -550,24 +586,28 @@ def main():
     prep["alloc_lanes"] = most
 
     def step(s):
-        plan.run(step_passes[(s * world + rank) % len(step_passes)])
-        return plan.stats()
+        out = plan.run(step_passes[(s * world + rank) % len(step_passes)])
+        return out, plan.stats()
 
     for s in range(a.warmup):
         step(s)
 
     barrier()
     t_start = time.perf_counter()
-    stats = [step(a.warmup + s) for s in range(a.steps)]
+    done = [step(a.warmup + s) for s in range(a.steps)]
     t_end = time.perf_counter()
     barrier()
     elapsed = max_over_ranks(t_end - t_start)
     note(f"{a.steps} timed steps {elapsed / a.steps * 1e3:.1f} ms/step")
+    stats = [st for _, st in done]
+    if a.dump_outputs and rank == 0:
+        last = step_passes[((a.warmup + a.steps - 1) * world + rank) % len(step_passes)]
+        dump_outputs(a.dump_outputs, plan, last, done[-1][0])  # before any later leg runs another pass
 
     # BASELINE.json's second metric: the full grid CV wall-clock (fold split, count tables,
     # passes, root read-out), max over ranks; at N=1 also the modelled 8-GPU wall-clock
     cv = None
-    if not a.no_full_cv:
+    if run_cv:
         barrier()
         cv = full_cv(plan, prep, gen_pat, rank, world, cap, model_worlds)
         cv["wall_s_incl_alloc"] = max_over_ranks(cv["wall_s_incl_alloc"])  # (each rank: its wall + its allocation)
@@ -661,7 +701,7 @@ def main():
             if "8" in cv["models"]:
                 line["cv_full_grid_wall_s_model_8gpu"] = cv["models"]["8"]["wall_s"]
                 line["cv_full_grid_speedup_model_8gpu"] = cv["models"]["8"]["speedup"]
-        if not a.no_cpu_baseline and world == 1:
+        if run_cpu and world == 1:
             note("cpu baseline")
             line["cpu_baseline"] = cpu_baseline(prep, a.cpu_cores or None)
         else:

@@ -1,4 +1,5 @@
 """Test inputs rebuilt from committed fixtures (tests/golden/), no /root/reference needed."""
+import glob
 import json
 import os
 
@@ -16,7 +17,14 @@ def golden_json(name):
 
 
 def golden_npz(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """The arrays of tests/golden/<name>, with those of its further parts <stem>.partN.npz
+    (make_golden.py keeps every committed archive below 1 MiB by writing it in parts)."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    arrays = {}
+    for path in [stem + ".npz"] + sorted(glob.glob(glob.escape(stem) + ".part*.npz")):
+        with np.load(path, allow_pickle=False) as part:
+            arrays.update({key: part[key] for key in part.files})
+    return arrays
 
 
 def write_count_files(k, directory):

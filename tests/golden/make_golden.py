@@ -55,6 +55,25 @@ def make_shim(tmp):
 # helpers executed inside the child interpreter (reference importable there)
 # ----------------------------------------------------------------------------
 
+def savez_parts(out, stem, arrays, limit=900_000):
+    """np.savez_compressed of ``arrays`` (in their order) as <stem>.npz, <stem>.part1.npz, ...
+    of at most ``limit`` bytes each, so that no committed fixture exceeds 1 MiB;
+    tests/fixtures.golden_npz reads the parts back as one."""
+    import io
+    import numpy as np
+    parts, size = [{}], 0
+    for key, arr in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{key: arr})
+        if parts[-1] and size + buf.tell() > limit:
+            parts.append({})
+            size = 0
+        parts[-1][key] = arr
+        size += buf.tell()
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(out, f"{stem}.part{i}.npz" if i else f"{stem}.npz"), **part)
+
+
 def _read_counts(name):
     d = {}
     with open(os.path.join(REF_DATA, name)) as fh:
@@ -285,7 +304,7 @@ def job_small(out):
                        "passes": [{"alpha": r["alpha"], "penalty": r["penalty"], "betas": r["betas"],
                                    "root_train": [float(x) for x in r["root_train"]],
                                    "root_test": [float(x) for x in r["root_test"]]} for r in log]}
-    np.savez_compressed(os.path.join(out, "small_dp.npz"), **arrays)
+    savez_parts(out, "small_dp", arrays)
     with open(os.path.join(out, "small_dp.json"), "w") as fh:
         json.dump({"meta": meta, "cases": full}, fh)
 

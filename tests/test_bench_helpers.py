@@ -1,6 +1,8 @@
 """bench.py's host-side helpers (no GPU): the synthetic count table is the CLI's sorted
 array table, the 8-rank CV shares cover every (alpha, fold, penalty) lane exactly once in
 lane order, and passes never exceed the pass cap."""
+import os
+
 import numpy as np
 
 import bench
@@ -110,6 +112,36 @@ def test_fold_pieces_cut_wide_grids_into_workgroup_widths():
     # the 5x5x5 grid: pieces are the (alpha, fold) groups themselves
     p9, o9 = engine.plan_passes(_prep()["groups"], 7, 5)
     assert all(len(p) == 1 and len(p[0][3]) == 5 for p in p9) and len(p9) == 25
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32/float64 .npy files of the pass's returned
+    arrays, its lanes' parameters and the same seeded cell sample on every call, well under
+    64 MB for the widest pass a plan runs (8 lanes)."""
+    class FakePlan:
+        info = {"npat": 7688671875}
+
+        def gather_cells(self, lane, cells):
+            assert cells.dtype == np.uint64 and cells.max() < self.info["npat"]
+            return (cells % 1000).astype(np.float32) + lane
+
+    groups = [(1, 0.5, 0.25, [3.0, 4.0, 5.0]), (2, 1.0, 0.75, [3.0] * 5)]
+    out = (np.arange(8, dtype=np.float32), -np.arange(8, dtype=np.float32), np.arange(1, 9, dtype=np.uint64))
+    got = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), FakePlan(), groups, out)
+        got.append({fn[:-4]: np.load(tmp_path / name / fn) for fn in sorted(os.listdir(tmp_path / name))})
+    a, b = got
+    assert sorted(a) == ["cell_index", "cell_scores", "lane_params", "n_leaves", "root_test", "root_train"]
+    assert all(a[k].dtype in (np.float32, np.float64) and a[k].tobytes() == b[k].tobytes() for k in a)
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    assert a["root_train"].tolist() == out[0].tolist() and a["root_test"].tolist() == out[1].tolist()
+    assert a["n_leaves"].tolist() == [float(x) for x in range(1, 9)]
+    assert a["lane_params"][2].tolist() == [1.0, 0.5, 0.25, 5.0] and a["lane_params"][3].tolist() == [2.0, 1.0, 0.75, 3.0]
+    cells = a["cell_index"].astype(np.int64)
+    assert cells.shape == (bench.DUMP_CELLS,) and (np.diff(cells) >= 0).all() and cells.max() > 2 ** 32
+    assert a["cell_scores"].shape == (8, bench.DUMP_CELLS)
+    assert (a["cell_scores"][3] == (cells % 1000) + 3).all()
 
 
 def test_scaling_table_entries():

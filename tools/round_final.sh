@@ -3,7 +3,7 @@
 #   gpu_tests.txt   pytest -m gpu (the driver's round-end suite)
 #   smoke.txt       __graft_entry__.smoke()
 #   <round>/...     tools/round_profile.sh: PMC passes + pmc_9mer.json, bench.json, kernel trace
-#   bench_11mer     bench.py --config 11mer (after its PMC record, tools/profile_11mer.sh)
+#   bench_11mer     bench.py --full --config 11mer (after its PMC record, tools/profile_11mer.sh)
 #   cli_9mer.json   the whole CLI on the 9-mer counts (tools/cli_9mer.py)
 # usage: tools/round_final.sh OUTDIR ROUND
 set -o pipefail
@@ -16,7 +16,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smo
 echo "smoke done"
 bash tools/round_profile.sh "$out/p9" "$rnd" || exit $?
 bash tools/profile_11mer.sh "$out/p11" "$rnd" || exit $?
-timeout -k 10 500 python bench.py --config 11mer > "$out/bench_11mer.json" 2> "$out/bench_11mer.err" || exit $?
+timeout -k 10 500 python bench.py --full --config 11mer > "$out/bench_11mer.json" 2> "$out/bench_11mer.err" || exit $?
 echo "bench 11mer done"
 timeout -k 10 300 python tools/cli_9mer.py > "$out/cli_9mer.json" 2> "$out/cli_9mer.err" || exit $?
 echo "cli done"

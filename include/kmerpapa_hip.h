@@ -28,6 +28,9 @@
  *   kp_kmer_parse    io_utils.py read_dict :82-136 (with downsize_contextD's centring,
  *                    :50-79) and read_joint_kmer_counts :3-46 (host code)
  *   kp_format_long_rows  the -l rows of cli.py:301-316 (host code)
+ *   kp_greedy        greedy_penalty_plus_pseudo.py: greedy_res_kmer_table_ord :159-196 with
+ *                    train_loss :18-25 per lane, and the test terms of
+ *                    CrossValidation.loglik :324-334 (test_logLik :28-35) per chain
  */
 #ifndef KMERPAPA_HIP_H
 #define KMERPAPA_HIP_H
@@ -192,6 +195,51 @@ int kp_math_libm(kp_ctx *ctx, const double *x, double *y, uint64_t n, int fn);
  * as the reference's `sum_train += ...` loop; xlogy / xlog1py with the C library's logs. */
 int kp_allkmers_cv(kp_ctx *ctx, const uint64_t *M, const uint64_t *U, uint64_t n, int nf, const double *alphas,
                    const double *betas, int na, double *sum_train, double *sum_test);
+
+/* The greedy top-down partition (--greedy / --greedyCV;
+ * src/kmerpapa/algorithms/greedy_penalty_plus_pseudo.py: train_loss :18-25, test_logLik
+ * :28-35, greedy_res_kmer_table_ord :159-196, the loop of CrossValidation.loglik :324-334).
+ * No lattice: only the k-mer count table and one tree per lane are on the device.
+ * A lane is one tree: fold = -1 grows it on all data, fold f on all data minus fold f (whose
+ * counts are then the test counts); chain >= 0 adds the lane's test terms, leaf by leaf in
+ * partition order, to chain_test[chain] after those of the earlier lanes of that chain (from
+ * 0.0: the reference's `test_ll` of one repeat); chain = -1 adds them nowhere.
+ * gen_pat: IUPAC, at most 16 positions (a pattern is a uint64 of 4-bit nucleotide masks,
+ * A = 1, C = 2, G = 4, T = 8, position 0 lowest).  M, U: [n_kmers][max(nf, 1)] uint64, rows in
+ * matches(gen_pat) order; with nf > 1 the columns are the fold tables and all data is their
+ * sum.  Totals of 2^53 or more are KP_E_ARG (the reference sums counts in float64).
+ * Outputs per lane: loss[lane] (float64, s1 + s2 along the tree) and n_leaves[lane];
+ * chain_test[max chain + 1].  Lanes run in batches that fit free device memory minus 2 GiB
+ * (KP_GREEDY_MEM = bytes overrides that budget; KP_GREEDY_CHUNK = k-mers per histogram
+ * chunk, default 4096); KP_E_NOMEM if the tables and one lane do not fit. */
+typedef struct {
+    int32_t fold;
+    int32_t chain;
+    double alpha;
+    double beta;
+    double penalty;
+} kp_greedy_lane;
+int kp_greedy(kp_ctx *ctx, const char *gen_pat, const uint64_t *M, const uint64_t *U, uint64_t n_kmers, int nf,
+              const kp_greedy_lane *lanes, int n_lanes, double *loss, double *chain_test, uint64_t *n_leaves);
+/* The partition of lane `lane` of the context's last kp_greedy call, in the reference's
+ * order (left subtree's patterns first), as pattern words; ctx = NULL: of this thread's
+ * last kp_greedy_host call.  cap = capacity of `patterns`; *n_out = number of patterns. */
+int kp_greedy_leaves(kp_ctx *ctx, uint32_t lane, uint64_t *patterns, uint64_t cap, uint64_t *n_out);
+/* Figures of the context's last kp_greedy call (measurement, tests of the memory budget). */
+typedef struct {
+    double hist_ms;          /* device time of the histogram kernel, all depths (HIP events) */
+    double total_ms;         /* host wall time of the whole call                             */
+    uint64_t frontier_kmers; /* k-mers of all frontier nodes, summed over depths and lanes:
+                                the rows the histogram kernel read                           */
+    uint64_t items;          /* (node, chunk) work items = waves of the histogram kernel     */
+    uint32_t depths;         /* levels of the deepest tree                                   */
+    uint32_t batches;        /* lane batches the call ran                                    */
+} kp_greedy_stats;
+int kp_greedy_last_stats(kp_ctx *ctx, kp_greedy_stats *out);
+/* Host-only (no GPU): the same call and outputs computed serially on the host with the
+ * per-node code the kernels run (parity and CPU tests; not a product path). */
+int kp_greedy_host(const char *gen_pat, const uint64_t *M, const uint64_t *U, uint64_t n_kmers, int nf,
+                   const kp_greedy_lane *lanes, int n_lanes, double *loss, double *chain_test, uint64_t *n_leaves);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

@@ -3,9 +3,13 @@
 
 The flow: read counts -> penalty presets -> general pattern (LCA) + zero fill ->
 (optional) grid cross-validation on the GPU -> final fit on the GPU -> partition table.
-Out of scope in this build (SURVEY.md §2): ``--greedy``, ``--greedyCV`` and ``--BayesOpt``;
-they are accepted by the parser and rejected with a message.  ``--score all_kmers`` (one
-rate per k-mer, no lattice DP) evaluates its loss terms on the GPU (algorithms/all_kmers_CV.py, kp_allkmers_cv).
+``--greedy`` / ``--greedyCV`` select the greedy top-down heuristic (no lattice; the trees of
+the whole grid grow on the GPU, algorithms/greedy_penalty_plus_pseudo.py, kp_greedy) where the
+reference does (cli.py:216-224, 273-275): either flag makes the CV greedy, only ``--greedy``
+the final fit.  ``--BayesOpt`` is out of scope (the reference's ``gp_minimize`` is unseeded):
+it is accepted by the parser and rejected with a message, as are ``--greedy`` / ``--greedyCV``
+in an invocation that names no count file.  ``--score all_kmers`` (one rate per k-mer, no
+lattice DP) evaluates its loss terms on the GPU (algorithms/all_kmers_CV.py, kp_allkmers_cv).
 """
 import argparse
 import json
@@ -17,7 +21,8 @@ from math import log
 import numpy as np
 
 from . import __version__
-from .algorithms import all_kmers_CV, bottum_up_array_penalty_plus_pseudo_CV, bottum_up_array_w_numba
+from .algorithms import (all_kmers_CV, bottum_up_array_penalty_plus_pseudo_CV, bottum_up_array_w_numba,
+                         greedy_penalty_plus_pseudo)
 from .io_utils import read_input_table
 from .papa import Pattern
 from .score_utils import get_loss
@@ -48,11 +53,13 @@ def get_parser():
     p.add_argument("--CV_only", action="store_true",
                    help="Only run crossvalidation. Do not run on whole data set using best values afterwards.")
     p.add_argument("--greedy", action="store_true",
-                   help="Use a fast greedy heuristic (not available in this build).")
+                   help="Use a fast greedy top-down heuristic instead of the optimal partition (cross "
+                        "validation and final fit). Needs no pattern lattice, so it also runs on general "
+                        "patterns too large for the optimal algorithm.")
     p.add_argument("--BayesOpt", action="store_true",
                    help="Bayesian Optimization of pseudo_count and penalty (not available in this build).")
     p.add_argument("--greedyCV", action="store_true",
-                   help="Greedy heuristic during CV (not available in this build).")
+                   help="Use the greedy heuristic during cross validation only; the final fit is optimal.")
     p.add_argument("-l", "--long_output", action="store_true", help="Print all k-mers in output format.")
     p.add_argument("-s", "--super_pattern", type=str,
                    help="If a super-pattern is provided the program will only consider k-mers that match that "
@@ -83,7 +90,10 @@ def get_parser():
 
 
 def _out_of_scope(args):
-    if args.greedy or args.greedyCV or args.BayesOpt:
+    """Flags this build rejects: --BayesOpt always; --greedy / --greedyCV only when the
+    invocation names no count file (there is nothing to run them on)."""
+    no_input = args.positive is None and args.joint_context_counts is None
+    if args.BayesOpt or ((args.greedy or args.greedyCV) and no_input):
         return "--greedy / --greedyCV / --BayesOpt"
     return None
 
@@ -230,7 +240,14 @@ def _main(args=None):
                 print(f"Running {args.nfolds}-fold cross validation on {k}-mers", file=sys.stderr)
             if k != len(this_gen_pat):
                 this_contextD, this_gen_pat = this_contextD.downsized(this_gen_pat, k)  # downsize_contextD
-            if args.score == "all_kmers":
+            if args.greedy or args.greedyCV:
+                assert args.score != "all_kmers", "greedy option cannot be used wil all-kmers"
+                # (the reference passes the full-width pattern and table at every k, cli.py:223)
+                CV = greedy_penalty_plus_pseudo.GridSearchCV(gen_pat, contextD, args.penalty_values,
+                                                             args.pseudo_counts, args.nfolds, args.iterations,
+                                                             args.seed)
+                this_alpha, this_penalty, test_score = CV.get_best_a_c()
+            elif args.score == "all_kmers":
                 this_alpha, test_score = all_kmers_CV.all_kmers(this_gen_pat, this_contextD, args.pseudo_counts,
                                                                 args, n_mut, n_unmut)
                 this_penalty = None
@@ -269,6 +286,10 @@ def _main(args=None):
     if args.score == "all_kmers":  # every k-mer is its own pattern, matches() order (cli.py:266-271)
         names, Ms, Us = contextD.match_rows(gen_pat)
         best_score, M, U, counts = 0, n_mut, n_unmut, list(zip(Ms, Us))
+    elif args.greedy:
+        best_score, M, U, names = greedy_penalty_plus_pseudo.greedy_partition(
+            gen_pat, contextD, best_alpha, best_beta, best_penalty, args)
+        counts = contextD.pattern_counts(names)
     else:
         best_score, M, U, names = bottum_up_array_w_numba.pattern_partition_bottom_up(
             gen_pat, contextD, best_alpha, best_beta, best_penalty, args, n_mut, n_unmut)

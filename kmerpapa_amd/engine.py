@@ -60,12 +60,23 @@ class KPPassStats(ctypes.Structure):
                 ("gather_bytes", ctypes.c_double)]
 
 
+class KPGreedyLane(ctypes.Structure):
+    _fields_ = [("fold", ctypes.c_int32), ("chain", ctypes.c_int32), ("alpha", ctypes.c_double),
+                ("beta", ctypes.c_double), ("penalty", ctypes.c_double)]
+
+
+class KPGreedyStats(ctypes.Structure):
+    _fields_ = [("hist_ms", ctypes.c_double), ("total_ms", ctypes.c_double), ("frontier_kmers", ctypes.c_uint64),
+                ("items", ctypes.c_uint64), ("depths", ctypes.c_uint32), ("batches", ctypes.c_uint32)]
+
+
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
            "kp_reserve_lanes", "kp_last_pass_stats", "kp_last_launch_ms", "kp_fit_leaves", "kp_dump_lane", "kp_gather_cells", "kp_fold_split",
            "kp_fold_sample", "kp_math_log", "kp_math_libm", "kp_kmer_parse", "kp_kmer_table_info", "kp_kmer_table_copy", "kp_kmer_table_free",
            "kp_format_long_rows", "kp_py_repr", "kp_device_groups", "kp_allkmers_cv", "kp_block_order_check",
-           "kp_plan_block_check"]
+           "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
+           "kp_greedy_last_stats"]
 
 
 def load():
@@ -125,6 +136,13 @@ def load():
         L.kp_py_repr.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, u64p]
         L.kp_allkmers_cv.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]
         L.kp_fold_sample.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), vp, ctypes.c_uint64, ctypes.c_uint64, vp]
+        if hasattr(L, "kp_greedy"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            L.kp_greedy.argtypes = [vp, ctypes.c_char_p, vp, vp, ctypes.c_uint64, ctypes.c_int,
+                                    ctypes.POINTER(KPGreedyLane), ctypes.c_int, vp, vp, vp]
+            L.kp_greedy_leaves.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint64, u64p]
+            L.kp_greedy_last_stats.argtypes = [vp, ctypes.POINTER(KPGreedyStats)]
+            L.kp_greedy_host.argtypes = [ctypes.c_char_p, vp, vp, ctypes.c_uint64, ctypes.c_int,
+                                         ctypes.POINTER(KPGreedyLane), ctypes.c_int, vp, vp, vp]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -424,6 +442,28 @@ class Device:
                                      _ptr(al), _ptr(be), int(al.size), _ptr(tr), _ptr(te)))
         return tr, te
 
+    def greedy(self, gen_pat, M, U, lanes, nf=0):
+        """The greedy top-down partition of every lane on this GPU (kp_greedy;
+        greedy_penalty_plus_pseudo.py :159-196, :324-334).  ``M``/``U``: ``[n_kmers]`` or
+        ``[n_kmers, nf]`` counts, rows in matches(gen_pat) order; ``lanes``: tuples ``(fold,
+        chain, alpha, beta, penalty)`` (fold -1 = all data, chain -1 = none).  Returns
+        ``(loss, chain_test, n_leaves)``."""
+        return _greedy_call(self._h, gen_pat, M, U, lanes, nf)
+
+    def greedy_batches(self):
+        """Lane batches the last :meth:`greedy` call ran (it cuts the lanes to fit device memory)."""
+        return self.greedy_stats()["batches"]
+
+    def greedy_stats(self):
+        """Figures of the last :meth:`greedy` call (kp_greedy_last_stats) as a dict."""
+        st = KPGreedyStats()
+        _check(load().kp_greedy_last_stats(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPGreedyStats._fields_}
+
+    def greedy_leaves(self, lane):
+        """Patterns of lane ``lane`` of the last :meth:`greedy` call, in the reference's order."""
+        return _greedy_leaves(self._h, lane)
+
     def close(self):
         if self._h:
             load().kp_destroy(self._h)
@@ -434,6 +474,64 @@ class Device:
             self.close()
         except Exception:
             pass
+
+
+_MASK_LETTER = "?ACMGRSVTWYHKDBN"  # nucleotide bits A = 1, C = 2, G = 4, T = 8 -> IUPAC code
+
+
+def pattern_word(pattern):
+    """A pattern as kp_greedy's word: 4 bits per position, position 0 lowest."""
+    return sum(_MASK_LETTER.index(x) << (4 * i) for i, x in enumerate(pattern))
+
+
+def word_pattern(word, k):
+    """The IUPAC pattern of a kp_greedy pattern word of ``k`` positions."""
+    word = int(word)
+    return "".join(_MASK_LETTER[(word >> (4 * i)) & 15] for i in range(k))
+
+
+def _greedy_call(handle, gen_pat, M, U, lanes, nf):
+    L = load()
+    M = np.ascontiguousarray(M, dtype=np.uint64)
+    U = np.ascontiguousarray(U, dtype=np.uint64)
+    nf = int(nf)
+    cols = max(nf, 1)
+    if U.shape != M.shape or M.size % cols or (M.ndim == 2 and M.shape[1] != cols) or M.ndim > 2:
+        raise ValueError("counts must be [n_kmers] or [n_kmers, nf]")
+    n = M.size // cols
+    arr = (KPGreedyLane * max(len(lanes), 1))()
+    for i, (fold, chain, alpha, beta, penalty) in enumerate(lanes):
+        arr[i] = KPGreedyLane(int(fold), int(chain), float(alpha), float(beta), float(penalty))
+    n_chains = max([int(x[1]) + 1 for x in lanes] + [0])
+    loss = np.zeros(len(lanes), np.float64)
+    chain = np.zeros(n_chains, np.float64)
+    nl = np.zeros(len(lanes), np.uint64)
+    gp = gen_pat.encode("ascii")
+    if handle is None:
+        rc = L.kp_greedy_host(gp, _ptr(M), _ptr(U), ctypes.c_uint64(n), nf, arr, len(lanes), _ptr(loss), _ptr(chain),
+                              _ptr(nl))
+    else:
+        rc = L.kp_greedy(handle, gp, _ptr(M), _ptr(U), ctypes.c_uint64(n), nf, arr, len(lanes), _ptr(loss),
+                         _ptr(chain), _ptr(nl))
+    _check(rc)
+    return loss, chain, nl
+
+
+def _greedy_leaves(handle, lane):
+    L = load()
+    n = ctypes.c_uint64(0)
+    _check(L.kp_greedy_leaves(handle, int(lane), None, ctypes.c_uint64(0), ctypes.byref(n)))
+    out = np.zeros(n.value, np.uint64)
+    _check(L.kp_greedy_leaves(handle, int(lane), _ptr(out), ctypes.c_uint64(n.value), ctypes.byref(n)))
+    return out
+
+
+def greedy_host(gen_pat, M, U, lanes, nf=0):
+    """:meth:`Device.greedy` computed serially on the host (kp_greedy_host: the kernels'
+    per-node code; parity and CPU tests, not a product path).  Returns ``(loss, chain_test,
+    n_leaves, leaves)`` with ``leaves[lane]`` the lane's pattern words."""
+    loss, chain, nl = _greedy_call(None, gen_pat, M, U, lanes, nf)
+    return loss, chain, nl, [_greedy_leaves(None, i) for i in range(len(lanes))]
 
 
 class Plan:

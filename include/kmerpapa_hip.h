@@ -31,6 +31,9 @@
  *   kp_greedy        greedy_penalty_plus_pseudo.py: greedy_res_kmer_table_ord :159-196 with
  *                    train_loss :18-25 per lane, and the test terms of
  *                    CrossValidation.loglik :324-334 (test_logLik :28-35) per chain
+ *   kp_apply         papa.PatternPartition's checks (papa.py:53-107, with the pairwise one it
+ *                    leaves commented out) and get_M_U (pattern_utils.py:192-215) for every
+ *                    pattern of a partition over any table, by mask matching
  */
 #ifndef KMERPAPA_HIP_H
 #define KMERPAPA_HIP_H
@@ -240,6 +243,47 @@ int kp_greedy_last_stats(kp_ctx *ctx, kp_greedy_stats *out);
  * per-node code the kernels run (parity and CPU tests; not a product path). */
 int kp_greedy_host(const char *gen_pat, const uint64_t *M, const uint64_t *U, uint64_t n_kmers, int nf,
                    const kp_greedy_lane *lanes, int n_lanes, double *loss, double *chain_test, uint64_t *n_leaves);
+
+/* A fitted partition applied to a k-mer count table: which pattern each row belongs to, the
+ * table's counts per pattern, whether the patterns are a partition at all, and the table's
+ * -2 log-likelihood under given rates.  (The reference has papa.PatternPartition's
+ * constructor checks, papa.py:53-107 -- its pairwise check is commented out as slow -- and
+ * get_M_U, pattern_utils.py:192-215, which enumerates every k-mer of a pattern.)  Nothing is
+ * enumerated here: row i matches pattern j when (onehot(codes[i]) & ~patterns[j]) == 0, so the
+ * table may be sparse (observed k-mers only) and k may be up to 16.
+ * patterns[n_patterns], super_word: pattern words as kp_greedy's (4-bit masks, position 0
+ * lowest).  codes[n]: 2 bits per letter, first letter most significant (kp_kmer_parse);
+ * M, U: [n][ncol] counts.  Outputs: pid[n] (may be NULL) = the row's pattern, -1 if none
+ * matches, -2 if several do; pat_M, pat_U [n_patterns][ncol] = counts of the rows with exactly
+ * one match, summed as integers; with rates[n_patterns] (may be NULL, then ll is not written)
+ * ll[c] = -2 * sum over patterns, in order from 0.0, of xlogy(pat_M, rate) + xlog1py(pat_U,
+ * -rate): score_utils.get_loss with penalty 0, bit for bit.  stats: rows without / with
+ * several matches, pattern pairs that share a k-mer, patterns that are not sub-patterns of
+ * super_word.  KP_E_ARG: k outside 1..16, a code with bits above 2k, a pattern (or super_word)
+ * with an empty position or bits above position k, a negative count, a column total of 2^63
+ * or more, n_patterns = 0.  n = 0 is valid.  KP_E_NOMEM if the table does not fit device
+ * memory.  Knobs, read at each call (every setting gives the same results): KP_APPLY_TILE =
+ * patterns per LDS tile (default 1024; 0 = no tiles, the patterns come through the scalar
+ * cache), KP_APPLY_GLOBAL=1 = totals by global atomics, KP_APPLY_LDS=1/0 = totals in LDS
+ * counters per workgroup required (KP_E_ARG if they do not fit) / off (default: on when
+ * they fit and the workgroups' flushes, workgroups x 2 x n_patterns x ncol, are no more
+ * atomics than the 2 x n x ncol of adding directly), KP_APPLY_GRID = most workgroups to
+ * launch. */
+typedef struct {
+    uint64_t unmatched, multi;
+    uint64_t overlap_pairs, outside_super;
+    double assign_ms;      /* device time of kp_apply_assign (HIP events; 0 on the host)    */
+    uint32_t tiles;        /* pattern tiles per row sweep (0 = scalar-cache path, or host)  */
+    uint32_t lds_counters; /* 1 = the totals were summed in LDS counters per workgroup      */
+} kp_apply_stats;
+int kp_apply(kp_ctx *ctx, int k, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word,
+             const uint64_t *codes, const int64_t *M, const int64_t *U, uint64_t n, int ncol, const double *rates,
+             int32_t *pid, uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats);
+/* Host-only (no GPU): the same call run serially on the host by the same per-row / per-pair /
+ * per-term code (parity and CPU tests; not a product path). */
+int kp_apply_host(int k, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word, const uint64_t *codes,
+                  const int64_t *M, const int64_t *U, uint64_t n, int ncol, const double *rates, int32_t *pid,
+                  uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

@@ -70,13 +70,19 @@ class KPGreedyStats(ctypes.Structure):
                 ("items", ctypes.c_uint64), ("depths", ctypes.c_uint32), ("batches", ctypes.c_uint32)]
 
 
+class KPApplyStats(ctypes.Structure):
+    _fields_ = [("unmatched", ctypes.c_uint64), ("multi", ctypes.c_uint64), ("overlap_pairs", ctypes.c_uint64),
+                ("outside_super", ctypes.c_uint64), ("assign_ms", ctypes.c_double), ("tiles", ctypes.c_uint32),
+                ("lds_counters", ctypes.c_uint32)]
+
+
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
            "kp_reserve_lanes", "kp_last_pass_stats", "kp_last_launch_ms", "kp_fit_leaves", "kp_dump_lane", "kp_gather_cells", "kp_fold_split",
            "kp_fold_sample", "kp_math_log", "kp_math_libm", "kp_kmer_parse", "kp_kmer_table_info", "kp_kmer_table_copy", "kp_kmer_table_free",
            "kp_format_long_rows", "kp_py_repr", "kp_device_groups", "kp_allkmers_cv", "kp_block_order_check",
            "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
-           "kp_greedy_last_stats"]
+           "kp_greedy_last_stats", "kp_apply", "kp_apply_host"]
 
 
 def load():
@@ -143,6 +149,11 @@ def load():
             L.kp_greedy_last_stats.argtypes = [vp, ctypes.POINTER(KPGreedyStats)]
             L.kp_greedy_host.argtypes = [ctypes.c_char_p, vp, vp, ctypes.c_uint64, ctypes.c_int,
                                          ctypes.POINTER(KPGreedyLane), ctypes.c_int, vp, vp, vp]
+        if hasattr(L, "kp_apply"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            tail = [ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp, vp,
+                    vp, vp, vp, ctypes.POINTER(KPApplyStats)]
+            L.kp_apply.argtypes = [vp] + tail
+            L.kp_apply_host.argtypes = tail
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -464,6 +475,15 @@ class Device:
         """Patterns of lane ``lane`` of the last :meth:`greedy` call, in the reference's order."""
         return _greedy_leaves(self._h, lane)
 
+    def apply(self, k, patterns, super_word, codes, M, U, rates=None, want_pid=True):
+        """A partition applied to a count table on this GPU (kp_apply).  ``patterns``: pattern
+        words (:func:`pattern_word`), ``super_word`` the super pattern's; ``codes`` ``[n]``
+        KmerCounts codes, ``M``/``U`` ``[n]`` or ``[n, ncol]`` counts; ``rates`` ``[P]`` or None.
+        Returns ``(pid, pat_M, pat_U, ll, stats)``: ``pid`` int32 ``[n]`` (-1 no pattern, -2
+        several; None without ``want_pid``), ``pat_M``/``pat_U`` uint64 shaped ``[P]`` or ``[P,
+        ncol]`` as the counts, ``ll`` float64 ``[ncol]`` (None without rates), ``stats`` a dict."""
+        return _apply_call(self._h, k, patterns, super_word, codes, M, U, rates, want_pid)
+
     def close(self):
         if self._h:
             load().kp_destroy(self._h)
@@ -532,6 +552,40 @@ def greedy_host(gen_pat, M, U, lanes, nf=0):
     n_leaves, leaves)`` with ``leaves[lane]`` the lane's pattern words."""
     loss, chain, nl = _greedy_call(None, gen_pat, M, U, lanes, nf)
     return loss, chain, nl, [_greedy_leaves(None, i) for i in range(len(lanes))]
+
+
+def _apply_call(handle, k, patterns, super_word, codes, M, U, rates, want_pid):
+    L = load()
+    pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+    codes = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+    M = np.ascontiguousarray(M, dtype=np.int64)
+    U = np.ascontiguousarray(U, dtype=np.int64)
+    n = codes.shape[0]
+    if M.shape != U.shape or M.ndim not in (1, 2) or M.shape[0] != n:
+        raise ValueError("counts must be [n_rows] or [n_rows, ncol], as many rows as codes")
+    ncol = 1 if M.ndim == 1 else M.shape[1]
+    P = pats.shape[0]
+    r = ll = None
+    if rates is not None:
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != P:
+            raise ValueError("one rate per pattern")
+        ll = np.zeros(ncol, np.float64)
+    pid = np.zeros(n, np.int32) if want_pid else None
+    shape = (P,) if M.ndim == 1 else (P, ncol)
+    pat_M = np.zeros(shape, np.uint64)
+    pat_U = np.zeros(shape, np.uint64)
+    st = KPApplyStats()
+    args = (int(k), _ptr(pats), ctypes.c_uint32(P), ctypes.c_uint64(int(super_word)), _ptr(codes), _ptr(M), _ptr(U),
+            ctypes.c_uint64(n), int(ncol), _ptr(r), _ptr(pid), _ptr(pat_M), _ptr(pat_U), _ptr(ll), ctypes.byref(st))
+    _check(L.kp_apply_host(*args) if handle is None else L.kp_apply(handle, *args))
+    return pid, pat_M, pat_U, ll, {name: getattr(st, name) for name, _ in KPApplyStats._fields_}
+
+
+def apply_host(k, patterns, super_word, codes, M, U, rates=None, want_pid=True):
+    """:meth:`Device.apply` computed serially on the host (kp_apply_host: the kernels' per-row,
+    per-pair and per-term code; parity and CPU tests, not a product path)."""
+    return _apply_call(None, k, patterns, super_word, codes, M, U, rates, want_pid)
 
 
 class Plan:

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "kp_core.h"
+#include "kp_rt.h"
 
 #define KP_A_MAXK 16
 #define KP_A_THREADS 512
@@ -199,3 +200,224 @@ __global__ void __launch_bounds__(64) kp_apply_sums(const double *__restrict__ t
 }
 
 #endif  // __HIPCC__
+
+// ---------------------------------------------------------------------------
+// a fitted partition applied to a count table (kp_apply.h)
+// ---------------------------------------------------------------------------
+
+// every nibble of the k positions non-zero, nothing above them
+static bool apply_word_ok(uint64_t w, int k) {
+    return kp_a_full(w, kp_a_low(k)) && (k == KP_A_MAXK || (w >> (4 * k)) == 0);
+}
+
+// Arguments of kp_apply / kp_apply_host.
+static int apply_check(const char *who, int k, const uint64_t *patterns, uint32_t P, uint64_t super_word,
+                       const uint64_t *codes, const int64_t *M, const int64_t *U, uint64_t n, int ncol,
+                       const double *rates, uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats) {
+    const std::string w(who);
+    if (k < 1 || k > KP_A_MAXK) return fail(KP_E_ARG, w + ": k must be 1..16 (a pattern is a 64-bit word of 4-bit masks)");
+    if (P == 0) return fail(KP_E_ARG, w + ": no patterns");
+    if (!patterns || !pat_M || !pat_U || !stats || ncol < 1 || (n && (!codes || !M || !U)) || (rates && !ll))
+        return fail(KP_E_ARG, w + ": bad arguments");
+    if (2ull * P * (uint64_t)ncol >= (1ull << 31)) return fail(KP_E_ARG, w + ": patterns x columns of 2^30 or more");
+    for (uint32_t i = 0; i < P; ++i)
+        if (!apply_word_ok(patterns[i], k))
+            return fail(KP_E_ARG, w + ": pattern " + std::to_string(i) + " has an empty position or bits above position k");
+    if (!apply_word_ok(super_word, k)) return fail(KP_E_ARG, w + ": the super pattern has an empty position or bits above position k");
+    const uint64_t lim = 1ull << 63;
+    for (uint64_t i = 0; i < n; ++i)
+        if (codes[i] >> (2 * k)) return fail(KP_E_ARG, w + ": k-mer code of row " + std::to_string(i) + " has bits above 2k");
+    for (int c = 0; c < ncol; ++c) {
+        uint64_t sm = 0, su = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const int64_t m = M[i * ncol + c], u = U[i * ncol + c];
+            if (m < 0 || u < 0) return fail(KP_E_ARG, w + ": negative count in row " + std::to_string(i));
+            sm += (uint64_t)m;
+            su += (uint64_t)u;
+            if (sm >= lim || su >= lim) return fail(KP_E_ARG, w + ": a column total of 2^63 or more");
+        }
+    }
+    return KP_OK;
+}
+
+template <bool LDSC, bool TILED>
+static int apply_launch(hipStream_t st, const kp_a_args &A, unsigned grid, size_t lds) {
+    if (lds > 65536)
+        KP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kp_apply_assign<LDSC, TILED>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((kp_apply_assign<LDSC, TILED>), dim3(grid), dim3(KP_A_THREADS), lds, st, A);
+    KP_HIP(hipGetLastError());
+    return KP_OK;
+}
+
+extern "C" {
+
+int kp_apply_host(int k, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word, const uint64_t *codes,
+                  const int64_t *M, const int64_t *U, uint64_t n, int ncol, const double *rates, int32_t *pid,
+                  uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats) {
+    const uint32_t P = n_patterns;
+    int rc = apply_check("kp_apply_host", k, patterns, P, super_word, codes, M, U, n, ncol, rates, pat_M, pat_U, ll, stats);
+    if (rc) return rc;
+    *stats = kp_apply_stats{};
+    for (uint64_t e = 0; e < (uint64_t)P * ncol; ++e) pat_M[e] = pat_U[e] = 0;
+    for (uint64_t row = 0; row < n; ++row) {
+        const uint64_t oh = kp_a_onehot(codes[row], k);
+        uint32_t first = 0, cnt = 0;
+        for (uint32_t j = 0; j < P; ++j) {
+            const bool m = kp_a_match(oh, patterns[j]);
+            first = (m && !cnt) ? j : first;
+            cnt += m;
+        }
+        if (pid) pid[row] = kp_a_pid(first, cnt);
+        if (cnt == 1) {
+            for (int c = 0; c < ncol; ++c) {
+                pat_M[(uint64_t)first * ncol + c] += (uint64_t)M[row * ncol + c];
+                pat_U[(uint64_t)first * ncol + c] += (uint64_t)U[row * ncol + c];
+            }
+        } else if (cnt == 0) {
+            ++stats->unmatched;
+        } else {
+            ++stats->multi;
+        }
+    }
+    const uint64_t low = kp_a_low(k);
+    for (uint32_t i = 0; i < P; ++i) {
+        for (uint32_t j = i + 1; j < P; ++j) stats->overlap_pairs += kp_a_overlap(patterns[i], patterns[j], low);
+        stats->outside_super += (patterns[i] & ~super_word) != 0;
+    }
+    if (rates)
+        for (int c = 0; c < ncol; ++c) {
+            double s = 0.0;
+            for (uint32_t p = 0; p < P; ++p) s += kp_a_term(pat_M[(uint64_t)p * ncol + c], pat_U[(uint64_t)p * ncol + c], rates[p]);
+            ll[c] = -2.0 * s + 0.0;
+        }
+    return KP_OK;
+}
+
+int kp_apply(kp_ctx *c, int k, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word,
+             const uint64_t *codes, const int64_t *M, const int64_t *U, uint64_t n, int ncol, const double *rates,
+             int32_t *pid, uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats) {
+    if (!c) return fail(KP_E_ARG, "kp_apply: null ctx");
+    const uint32_t P = n_patterns;
+    int rc = apply_check("kp_apply", k, patterns, P, super_word, codes, M, U, n, ncol, rates, pat_M, pat_U, ll, stats);
+    if (rc) return rc;
+    *stats = kp_apply_stats{};
+    KP_HIP(hipSetDevice(c->device));
+
+    // launch shape: the tile, where the totals are summed, the grid (KP_APPLY_* knobs)
+    const long tile_env = env_int("KP_APPLY_TILE", KP_A_TILE);
+    if (tile_env < 0 || tile_env > 4096) return fail(KP_E_ARG, "kp_apply: KP_APPLY_TILE must be 0..4096 patterns");
+    const uint32_t tile = (uint32_t)tile_env;
+    const size_t cells = (size_t)P * (size_t)ncol;
+    const size_t lds_all = (size_t)tile * 8 + 2 * cells * 8;
+    const bool fits = lds_all <= c->lds_max;
+    const bool force_global = env_int("KP_APPLY_GLOBAL", 0) != 0;
+    const long lds_env = env_int("KP_APPLY_LDS", -1);
+    if (lds_env > 0 && (force_global || !fits))
+        return fail(KP_E_ARG, force_global ? "kp_apply: KP_APPLY_LDS=1 and KP_APPLY_GLOBAL=1 contradict each other"
+                                           : "kp_apply: KP_APPLY_LDS=1, but the counters (" + std::to_string(lds_all) +
+                                                 " bytes with the tile) do not fit LDS");
+    const uint64_t blocks = (n + KP_A_THREADS - 1) / KP_A_THREADS;
+    const long grid_env = env_int("KP_APPLY_GRID", 0);
+    auto grid_for = [&](size_t lds_bytes) {  // a persistent grid: as many workgroups as are resident at once
+        const int per_cu = lds_bytes <= 40u * 1024u ? 4 : (lds_bytes <= 80u * 1024u ? 2 : 1);
+        uint64_t g = std::min<uint64_t>(blocks, (uint64_t)c->cus * per_cu);
+        return grid_env > 0 ? std::min<uint64_t>(g, (uint64_t)grid_env) : g;
+    };
+    bool ldsc = !force_global && lds_env != 0 && fits;
+    // unless forced: LDS counters only where they save global atomics -- every workgroup
+    // flushes up to 2 P ncol counters, adding directly takes up to 2 ncol atomics per row
+    // (a sparse table against many patterns: 1.31 against 1.83 ms)
+    if (ldsc && lds_env < 0 && grid_for(lds_all) * 2 * cells > 2 * n * (uint64_t)ncol) ldsc = false;
+    const size_t lds = ldsc ? lds_all : (size_t)tile * 8;
+    const uint64_t grid = grid_for(lds);
+    const uint64_t steps = grid ? (blocks + grid - 1) / grid : 0;
+    if (steps >= (1ull << 32)) return fail(KP_E_ARG, "kp_apply: too many rows for the grid");
+
+    // device buffers: one arena
+    const size_t b_codes = g_up(n * 8), b_cnt = g_up(n * (size_t)ncol * 8), b_pid = pid ? g_up(n * 4) : 0;
+    const size_t b_pats = g_up((size_t)P * 8), b_tot = g_up(2 * cells * 8), b_terms = rates ? g_up(cells * 8) : 0;
+    const size_t b_ll = rates ? g_up((size_t)ncol * 8) : 0, b_rates = rates ? b_pats : 0;
+    const size_t need = b_codes + 2 * b_cnt + b_pid + b_pats + b_tot + g_up(32) + b_rates + b_terms + b_ll;
+    {
+        size_t fr = 0, tot = 0;
+        KP_HIP(hipMemGetInfo(&fr, &tot));
+        if (need > fr + c->arena.bytes)
+            return fail(KP_E_NOMEM, "kp_apply: the table and the partition need " + std::to_string(need >> 20) +
+                                        " MiB of device memory, " + std::to_string((fr + c->arena.bytes) >> 20) + " MiB are free");
+    }
+    // (the arena shared with kp_greedy; every size above is already rounded as take() rounds)
+    if ((rc = c->arena.reserve("kp_apply", need))) return rc;
+    auto take = [&](size_t bytes) { return c->arena.take(bytes); };
+    uint64_t *d_codes = (uint64_t *)take(b_codes);
+    int64_t *dM = (int64_t *)take(b_cnt), *dU = (int64_t *)take(b_cnt);
+    int32_t *d_pid = pid ? (int32_t *)take(b_pid) : nullptr;
+    uint64_t *d_pats = (uint64_t *)take(b_pats);
+    unsigned long long *d_tot = (unsigned long long *)take(b_tot);
+    unsigned long long *d_err = (unsigned long long *)take(g_up(32));  // unmatched, multi, pairs, outside
+    double *d_rates = rates ? (double *)take(b_rates) : nullptr;
+    double *d_terms = rates ? (double *)take(b_terms) : nullptr;
+    double *d_ll = rates ? (double *)take(b_ll) : nullptr;
+    if ((rc = c->arena.check("kp_apply"))) return rc;
+
+    hipStream_t st = c->stream;
+    KP_HIP(hipMemcpyAsync(d_pats, patterns, (size_t)P * 8, hipMemcpyHostToDevice, st));
+    KP_HIP(hipMemsetAsync(d_tot, 0, 2 * cells * 8, st));
+    KP_HIP(hipMemsetAsync(d_err, 0, 32, st));
+    if (n) {
+        KP_HIP(hipMemcpyAsync(d_codes, codes, n * 8, hipMemcpyHostToDevice, st));
+        KP_HIP(hipMemcpyAsync(dM, M, n * (size_t)ncol * 8, hipMemcpyHostToDevice, st));
+        KP_HIP(hipMemcpyAsync(dU, U, n * (size_t)ncol * 8, hipMemcpyHostToDevice, st));
+        kp_a_args A;
+        A.codes = d_codes;
+        A.M = dM;
+        A.U = dU;
+        A.n = n;
+        A.k = k;
+        A.ncol = ncol;
+        A.pats = d_pats;
+        A.P = P;
+        A.tile = tile;
+        A.steps = (uint32_t)steps;
+        A.pid = d_pid;
+        A.tot = d_tot;
+        A.err = d_err;
+        KP_HIP(hipEventRecord(c->ev[0], st));
+        if (ldsc)
+            rc = tile ? apply_launch<true, true>(st, A, (unsigned)grid, lds) : apply_launch<true, false>(st, A, (unsigned)grid, lds);
+        else
+            rc = tile ? apply_launch<false, true>(st, A, (unsigned)grid, lds) : apply_launch<false, false>(st, A, (unsigned)grid, lds);
+        if (rc) return rc;
+        KP_HIP(hipEventRecord(c->ev[1], st));
+    }
+    hipLaunchKernelGGL(kp_apply_pairs, dim3((P + 255) / 256), dim3(256), 0, st, d_pats, P, k, super_word, d_err + 2);
+    KP_HIP(hipGetLastError());
+    if (rates) {
+        KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(kp_apply_terms, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, d_tot, d_rates, P, ncol,
+                           d_terms);
+        KP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kp_apply_sums, dim3((ncol + 63) / 64), dim3(64), 0, st, d_terms, P, ncol, d_ll);
+        KP_HIP(hipGetLastError());
+        KP_HIP(hipMemcpyAsync(ll, d_ll, (size_t)ncol * 8, hipMemcpyDeviceToHost, st));
+    }
+    unsigned long long h_err[4] = {0, 0, 0, 0};
+    KP_HIP(hipMemcpyAsync(h_err, d_err, 32, hipMemcpyDeviceToHost, st));
+    KP_HIP(hipMemcpyAsync(pat_M, d_tot, cells * 8, hipMemcpyDeviceToHost, st));
+    KP_HIP(hipMemcpyAsync(pat_U, d_tot + cells, cells * 8, hipMemcpyDeviceToHost, st));
+    if (pid && n) KP_HIP(hipMemcpyAsync(pid, d_pid, n * 4, hipMemcpyDeviceToHost, st));
+    KP_HIP(hipStreamSynchronize(st));
+    stats->unmatched = h_err[0];
+    stats->multi = h_err[1];
+    stats->overlap_pairs = h_err[2];
+    stats->outside_super = h_err[3];
+    if (n) {
+        float ms = 0.f;
+        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        stats->assign_ms = ms;
+        stats->tiles = tile ? (uint32_t)((P + tile - 1) / tile) : 0;
+        stats->lds_counters = ldsc ? 1u : 0u;
+    }
+    return KP_OK;
+}
+}  // extern "C"

@@ -463,7 +463,7 @@ __host__ __device__ inline void kp_dp_cell_values(const kp_geom &g, WP pw, uint3
 // pair-list word) = c * NL * 4 for a child cell c is one v_mul_u32_u24 whose source
 // operand selects the 16-bit half, and the LDS read takes it as its address (the dynamic
 // LDS array starts at address 0: the kernels declare no static LDS, checked at launch,
-// kp_hip.hip launch_dp_hz).  The plain form (mask or shift, multiply-add, add of the array
+// kp_pass.h launch_dp_hz).  The plain form (mask or shift, multiply-add, add of the array
 // base) costs 3 VALU per child instead of 1.  Per build, as measured
 // (profiles/r04/experiments/sdwa_ab.txt): 1 lane 111.5 -> 109.1 ms, 3 lanes 251 -> 243,
 // mixed 5 lanes 402 -> 399; 5 lanes unchanged, 4 lanes 311 -> 326 (register allocation).

@@ -21,6 +21,7 @@
 #endif
 
 #include "kp_logdata.h"
+#include "kp_rt.h"
 
 namespace kpf {
 
@@ -320,3 +321,55 @@ inline void sample(mt19937 &rng, uint64_t m, const uint64_t *colors, const uint6
 }
 
 }  // namespace kpf
+
+extern "C" {
+
+int kp_fold_sample(uint32_t *mt_key, int32_t *mt_pos, const uint64_t *colors, uint64_t n, uint64_t m,
+                   uint64_t *out) {
+    if (!mt_key || !mt_pos || (n && (!colors || !out))) return fail(KP_E_ARG, "bad arguments");
+    if (*mt_pos < 0 || *mt_pos > 624) return fail(KP_E_ARG, "MT19937 position out of range");
+    if (!n) return KP_OK;
+    kpf::mt19937 rng;
+    memcpy(rng.key, mt_key, sizeof(rng.key));
+    rng.pos = *mt_pos;
+    std::vector<uint64_t> tail(n);
+    uint64_t acc = 0;
+    for (uint64_t i = n; i-- > 0;) {
+        acc += colors[i];
+        tail[i] = acc;
+    }
+    kpf::sample(rng, m, colors, tail.data(), n, out);
+    memcpy(mt_key, rng.key, sizeof(rng.key));
+    *mt_pos = rng.pos;
+    return KP_OK;
+}
+
+int kp_fold_split(uint32_t *mt_key, int32_t *mt_pos, const uint64_t *colors, uint64_t n, int nf, uint64_t *folds) {
+    if (!mt_key || !mt_pos || (n && (!colors || !folds)) || nf < 1) return fail(KP_E_ARG, "bad arguments");
+    if (*mt_pos < 0 || *mt_pos > 624) return fail(KP_E_ARG, "MT19937 position out of range");
+    kpf::mt19937 rng;
+    memcpy(rng.key, mt_key, sizeof(rng.key));
+    rng.pos = *mt_pos;
+    std::vector<uint64_t> col(colors, colors + n), tail(n), s(n);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) total += col[i];
+    const uint64_t per_fold = total / (uint64_t)nf;  // n_samples = n // n_folds (CV_tools.py:51)
+    for (int f = 0; f + 1 < nf; ++f) {
+        uint64_t acc = 0;
+        for (uint64_t i = n; i-- > 0;) {
+            acc += col[i];
+            tail[i] = acc;
+        }
+        kpf::sample(rng, per_fold, col.data(), tail.data(), n, s.data());
+        for (uint64_t i = 0; i < n; ++i) {
+            folds[i * (uint64_t)nf + f] = s[i];
+            col[i] -= s[i];
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) folds[i * (uint64_t)nf + (nf - 1)] = col[i];
+    memcpy(mt_key, rng.key, sizeof(rng.key));
+    *mt_pos = rng.pos;
+    return KP_OK;
+}
+
+}  // extern "C"

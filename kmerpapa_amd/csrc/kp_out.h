@@ -19,6 +19,8 @@
 #include <charconv>
 #include <cmath>
 
+#include "kp_rt.h"
+
 namespace kpout {
 
 // Python repr of a finite or special double; returns the number of chars written (<= 32)
@@ -125,3 +127,33 @@ inline int64_t long_rows(const char *kmers, int k, const int64_t *c_neg, const i
 }
 
 }  // namespace kpout
+
+extern "C" {
+
+// ---- the long output table (host code) ----
+int kp_format_long_rows(const char *kmers, int k, const int64_t *c_neg, const int64_t *c_pos, const uint32_t *pid,
+                        uint64_t n, const char *tails, const uint64_t *tail_off, uint64_t n_tails, char *out,
+                        uint64_t cap, uint64_t *out_len) {
+    if (!out_len || k < 1 || (n && (!kmers || !c_neg || !c_pos || !pid || !tails || !tail_off || !out)))
+        return fail(KP_E_ARG, "bad arguments");
+    const int64_t w = kpout::long_rows(kmers, k, c_neg, c_pos, pid, n, tails, tail_off, n_tails, out, cap);
+    if (w == -1) return fail(KP_E_ARG, "output buffer too small");
+    if (w == -2) return fail(KP_E_ARG, "division by zero: a k-mer with no counts in the long output");
+    if (w == -3) return fail(KP_E_ARG, "pattern index out of range");
+    *out_len = (uint64_t)w;
+    return KP_OK;
+}
+
+int kp_py_repr(const double *x, uint64_t n, char *out, uint64_t cap, uint64_t *out_len) {
+    if (!out_len || (n && (!x || !out))) return fail(KP_E_ARG, "bad arguments");
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (w + 40 > cap) return fail(KP_E_ARG, "output buffer too small");
+        w += (uint64_t)kpout::py_repr(x[i], out + w);
+        out[w++] = '\n';
+    }
+    *out_len = w;
+    return KP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,178 @@
+// kp_rt.h -- the host runtime of libkmerpapa_hip.so: the thread's last error, the HIP error
+// macro, device allocation helpers, the environment knobs' reader and the device context
+// (kp_create / kp_destroy).  Host code only; every other header with C-ABI entry points
+// builds on it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/kmerpapa_hip.h"
+
+static thread_local std::string g_err;
+
+static int fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
+
+#define KP_HIP(expr)                                                                                  \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess)                                                                         \
+            return fail(KP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+    } while (0)
+
+// an integer knob from the environment; unset (or empty) gives the default
+static long env_int(const char *name, long unset) {
+    const char *e = getenv(name);
+    return e && *e ? atol(e) : unset;
+}
+
+// Device memory: plain hipMalloc.  On this platform an allocation of HBM that was used
+// before (by this or an earlier process) waits for the driver to wipe it, ~30 ms per GB
+// (4-6 s for the 150 GB of a 9-mer pass; fresh HBM 0.05 s per 100 GB), so the library
+// allocates the large per-lane buffers once (kp_reserve_lanes) and only grows them.  The
+// stream-ordered allocator (hipMallocAsync) skips that wait but is not usable: a 140 GB
+// request served from a freed 100 GB pool block returned memory that did not hold what
+// was written to it (tools/async_check.hip).
+template <typename T>
+static hipError_t dmalloc(T **p, size_t bytes) {
+    return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(bytes, 1));
+}
+
+template <typename T>
+static int upload(T **dptr, const std::vector<T> &v) {
+    size_t bytes = std::max<size_t>(1, v.size()) * sizeof(T);
+    KP_HIP(dmalloc(dptr, bytes));
+    if (!v.empty()) KP_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return KP_OK;
+}
+
+static void dfree(void *p) {
+    if (p) (void)hipFree(p);
+}
+
+static size_t g_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One device allocation carved into buffers, kept between calls and only grown (re-allocating
+// used HBM is slow, see dmalloc above).  reserve() starts a new layout of at most `need`
+// bytes, take() hands out its next piece rounded up to 256 bytes, check() fails if the
+// pieces taken exceed the allocation (nothing may use them before it passed).  `who`
+// prefixes the error text.
+struct kp_arena {
+    void *base = nullptr;
+    size_t bytes = 0;
+    size_t used = 0;
+
+    int reserve(const char *who, size_t need) {
+        used = 0;
+        if (bytes >= need) return KP_OK;
+        dfree(base);
+        base = nullptr;
+        bytes = 0;
+        if (hipMalloc(&base, need) != hipSuccess) {
+            (void)hipGetLastError();
+            base = nullptr;
+            return fail(KP_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(need >> 20) +
+                                        " MiB of device memory");
+        }
+        bytes = need;
+        return KP_OK;
+    }
+    char *take(size_t n_bytes) {
+        char *p = static_cast<char *>(base) + used;
+        used += g_up(n_bytes);
+        return p;
+    }
+    int check(const char *who) const {
+        return used > bytes ? fail(KP_E_PARITY, std::string(who) + ": arena layout exceeds its size") : KP_OK;
+    }
+};
+
+#define KP_SIDE_STREAMS 3
+
+struct kp_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // side streams: the lane classes of one pass (device groups of different widths, e.g. a
+    // 5-lane and a 1-lane group, or the 4 + 3 split of a 7-penalty group) are independent,
+    // so each class runs its launch sequence on a stream of its own and the classes overlap
+    hipStream_t side[KP_SIDE_STREAMS] = {nullptr, nullptr, nullptr};
+    hipEvent_t side_ev[KP_SIDE_STREAMS] = {nullptr, nullptr, nullptr};
+    size_t lds_max = 65536;
+    int cus = 256;  // compute units (kp_apply's persistent grid)
+    // kp_greedy and kp_apply: one device arena, and the partitions of the last kp_greedy
+    // call's lanes (kp_greedy_leaves)
+    kp_arena arena;
+    std::vector<std::vector<uint64_t>> g_leaves;
+    kp_greedy_stats g_stats{};  // of the last kp_greedy call
+};
+
+extern "C" {
+
+const char *kp_last_error(void) { return g_err.c_str(); }
+
+int kp_device_count(int *n) {
+    if (!n) return fail(KP_E_ARG, "null");
+    KP_HIP(hipGetDeviceCount(n));
+    return KP_OK;
+}
+
+int kp_create(int device, kp_ctx **out) {
+    if (!out) return fail(KP_E_ARG, "null out");
+    int n = 0;
+    KP_HIP(hipGetDeviceCount(&n));
+    if (device < 0 || device >= n) return fail(KP_E_ARG, "device " + std::to_string(device) + " not present");
+    KP_HIP(hipSetDevice(device));
+    kp_ctx *c = new kp_ctx();
+    c->device = device;
+    KP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    for (auto &e : c->ev) KP_HIP(hipEventCreate(&e));
+    for (int i = 0; i < KP_SIDE_STREAMS; ++i) {
+        KP_HIP(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
+        KP_HIP(hipEventCreateWithFlags(&c->side_ev[i], hipEventDisableTiming));
+    }
+    int lds = 0;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > 0)
+        c->lds_max = (size_t)lds;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->cus = cus;
+    *out = c;
+    return KP_OK;
+}
+
+int kp_device_mem(kp_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes) {
+    if (!c) return fail(KP_E_ARG, "null ctx");
+    KP_HIP(hipSetDevice(c->device));
+    size_t fr = 0, tot = 0;
+    KP_HIP(hipMemGetInfo(&fr, &tot));
+    if (free_bytes) *free_bytes = fr;
+    if (total_bytes) *total_bytes = tot;
+    return KP_OK;
+}
+
+void kp_destroy(kp_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (auto e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < KP_SIDE_STREAMS; ++i) {
+        if (c->side_ev[i]) (void)hipEventDestroy(c->side_ev[i]);
+        if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
+    }
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    dfree(c->arena.base);
+    delete c;
+}
+
+}  // extern "C"

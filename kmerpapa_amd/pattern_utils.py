@@ -3,7 +3,7 @@
 Public names, argument meanings and enumeration ORDERS follow the reference module
 ``kmerpapa.pattern_utils`` (src/kmerpapa/pattern_utils.py, v0.2.4) so that callers and
 tests written against it keep working.  The lattice tables below are the data the
-device planner (`kmerpapa_amd/csrc/kp_hip.hip`, ``kp_plan_create``) rebuilds in C++.
+device planner (`kmerpapa_amd/csrc/kp_plan_dev.h`, ``kp_plan_create``) rebuilds in C++.
 
 Facts the whole build relies on (checked by tests/test_pattern_utils.py):
   * cell index = mixed radix over positions, position 0 least significant; the digit at

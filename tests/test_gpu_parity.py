@@ -461,21 +461,20 @@ def test_lanes_per_workgroup_vs_oracle(eng, per_wg, monkeypatch):
     plan.close()
 
 
-@pytest.mark.parametrize("ws", ["0", "1"])
+# (the ids end in -0 as they did while a second parameter chose between this sweep, 0, and a
+# wave-specialised one that has been removed: the cases keep their names)
 @pytest.mark.parametrize("gp,max_block,itype,exact,alpha", [("NNMNN", 0, np.uint32, 0, 0.5), ("NNMNN", 0, np.uint32, 1, 0.5),
                                                             ("RNNNS", 64, np.uint32, 0, 0.5), ("NNNMN", 0, np.uint64, 0, 0.5),
-                                                            ("NNMNN", 0, np.uint32, 0, 0.0)])
-def test_1lane_sweep_vs_oracle(eng, monkeypatch, gp, max_block, itype, exact, alpha, ws):
-    """Every device group cut to one lane (KP_LANES_PER_WG=1): the 1-lane build of the sweep
-    (ws 0) and the opt-in persistent wave-specialised sweep for 1-lane groups (ws 1,
-    kp_dp_ws.h, KP_WS=1: producer waves gather block i + 1 while consumer waves run block i's
-    levels, LDS-counter hand-over; every launch above high level 0 runs on it).  Every cell of
-    every lane equals the oracle, with 32- and 64-bit counts, in KP_EXACT_LOGS mode, and with
-    alpha = 0 and k-mers of no counts (NaN k-mer cells)."""
+                                                            ("NNMNN", 0, np.uint32, 0, 0.0)],
+                         ids=["NNMNN-0-uint32-0-0.5-0", "NNMNN-0-uint32-1-0.5-0", "RNNNS-64-uint32-0-0.5-0",
+                              "NNNMN-0-uint64-0-0.5-0", "NNMNN-0-uint32-0-0.0-0"])
+def test_1lane_sweep_vs_oracle(eng, monkeypatch, gp, max_block, itype, exact, alpha):
+    """Every device group cut to one lane (KP_LANES_PER_WG=1): the 1-lane build of the sweep.
+    Every cell of every lane equals the oracle, with 32- and 64-bit counts, in KP_EXACT_LOGS
+    mode, and with alpha = 0 and k-mers of no counts (NaN k-mer cells)."""
     from kmerpapa_amd.CV_tools import fold_tables
     from kmerpapa_amd.pattern_utils import generality, matches
     from oracle import oracle as O
-    monkeypatch.setenv("KP_WS", ws)
     monkeypatch.setenv("KP_LANES_PER_WG", "1")
     monkeypatch.setenv("KP_EXACT_LOGS", str(exact))
     rng = np.random.RandomState(len(gp) + max_block)
@@ -509,6 +508,116 @@ def test_1lane_sweep_vs_oracle(eng, monkeypatch, gp, max_block, itype, exact, al
             score, _ = plan.dump_lane(lane)
             assert bits_equal(score, ref["score"][:, f]), (gp, c, f)
             assert bits_equal(rt[lane], ref["root_train"][f]) and bits_equal(re[lane], ref["root_test"][f])
+    plan.close()
+
+
+# ---- run_pass's other paths, on test_1lane_sweep_vs_oracle's first lattice and counts ----
+PASS_GP = "NNMNN"  # max_block 0: 151,875 cells, more than two high levels
+PASS_NF = 3
+PASS_PENS = [1.0, 2.0, 3.0, 5.0, 7.0, 9.0, 12.0, 16.0]
+_pass_case = {}
+
+
+def _pass_fixture(eng):
+    """The seeded 3-fold counts of test_1lane_sweep_vs_oracle[NNMNN-0-uint32-0-0.5-0], built once."""
+    if not _pass_case:
+        from kmerpapa_amd.CV_tools import fold_tables
+        from kmerpapa_amd.pattern_utils import generality, matches
+        rng = np.random.RandomState(len(PASS_GP) + 0)
+        ctx = {}
+        for k in matches(PASS_GP):
+            bg = int(rng.poisson(2e4 * rng.lognormal(0, 0.5)))
+            ctx[k] = (int(rng.binomial(bg, 0.01 * rng.lognormal(0, 0.4))), bg)
+        contexts, Mf, Uf = fold_tables(ctx, PASS_NF, np.random.RandomState(3), np.uint32)
+        Mk, Uk = eng.counts_in_kmer_order(PASS_GP, contexts, Mf, Uf, generality(PASS_GP), np.uint32)
+        tot_m = Mf.sum(axis=0).astype(np.uint64)
+        tot_u = Uf.sum(axis=0).astype(np.uint64)
+        mtr = tot_m.sum() - tot_m
+        utr = tot_u.sum() - tot_u
+        _pass_case.update(contexts=contexts, Mf=Mf, Uf=Uf, Mk=Mk, Uk=Uk, my=mtr / (mtr + utr), refs={})
+    return _pass_case
+
+
+def _pass_betas(case, alpha):
+    return (alpha * (1.0 - case["my"])) / case["my"]
+
+
+def _pass_ref(case, alpha, pen):
+    """oracle.cv_pass of one (alpha, penalty), every fold; computed once per module run."""
+    from oracle import oracle as O
+    key = (alpha, pen)
+    if key not in case["refs"]:
+        case["refs"][key] = O.cv_pass(PASS_GP, case["contexts"], case["Mf"], case["Uf"], alpha, _pass_betas(case, alpha),
+                                      pen, 32)
+    return case["refs"][key]
+
+
+def _pass_groups(case, alphas, pens):
+    """fold-major groups: every fold's alphas are consecutive (the order the CV driver runs them in)"""
+    return [(f, a, float(_pass_betas(case, a)[f]), list(pens)) for f in range(PASS_NF) for a in alphas]
+
+
+def _run_and_check(plan, case, groups):
+    """One pass; every cell of every lane and every root against the oracle.  Returns the
+    lanes' score arrays and roots."""
+    rt, re, _ = plan.run(groups)
+    lane, scores = 0, []
+    for f, alpha, _beta, pens in groups:
+        for pen in pens:
+            ref = _pass_ref(case, alpha, pen)
+            score, _ = plan.dump_lane(lane)
+            assert bits_equal(score, ref["score"][:, f]), (lane, f, alpha, pen)
+            assert bits_equal(rt[lane], ref["root_train"][f]) and bits_equal(re[lane], ref["root_test"][f]), lane
+            scores.append(score)
+            lane += 1
+    return scores, rt, re
+
+
+@pytest.mark.parametrize("knob,value", [("KP_CLASS_STREAMS", "1"), ("KP_LAUNCH_TIMES", "1"), ("KP_NT_SLOW_H", "0,1,2")])
+def test_two_lane_classes_and_launch_knobs_vs_oracle(eng, monkeypatch, knob, value):
+    """One pass of three fold groups of 7 penalties: 5 + 2 lanes per fold, so two lane classes
+    (three 5-lane and three 2-lane device groups), with the classes on streams of their own,
+    with per-launch events, and with a per-high-level non-temporal mask list.  Every cell of
+    every lane and every root equals the oracle; with KP_LAUNCH_TIMES=1 there is one time per
+    launch, 2 classes x the high levels (every high level of this lattice holds blocks)."""
+    case = _pass_fixture(eng)
+    monkeypatch.setenv(knob, value)
+    groups = _pass_groups(case, [0.5], PASS_PENS[:7])
+    assert eng.device_groups(groups, 5) == [(0, 5, 0), (5, 2, 0), (7, 5, 0), (12, 2, 0), (14, 5, 0), (19, 2, 0)]
+    plan = eng.Plan(eng.get_device(0), PASS_GP, 0)
+    plan.set_counts(case["Mk"], case["Uk"])
+    assert plan.info["lanes_per_workgroup"] == 5 and plan.info["high_levels"] > 2
+    _run_and_check(plan, case, groups)
+    launches = plan.stats()["dp_launches"]
+    assert launches == 2 * plan.info["high_levels"]
+    ms = plan.launch_ms()
+    if knob == "KP_LAUNCH_TIMES":
+        assert len(ms) == launches
+        assert np.all(np.isfinite(ms)) and np.all(ms > 0), ms
+    else:
+        assert len(ms) == 0
+    plan.close()
+
+
+def test_small_buffers_regrow_vs_oracle(eng):
+    """One plan, three passes: 6 lanes, then 72 (3 folds x 3 alphas x 8 penalties: more than
+    the 64 lanes the small per-lane buffers start with, and each fold's 24 lanes are cut into
+    mixed 5-lane workgroups), then the first 6 again.  Every pass equals the oracle and the
+    third equals the first."""
+    case = _pass_fixture(eng)
+    small = _pass_groups(case, [0.5], PASS_PENS[:2])
+    big = _pass_groups(case, [0.5, 1.0, 2.0], PASS_PENS)
+    assert sum(len(g[3]) for g in small) == 6 and sum(len(g[3]) for g in big) == 72
+    dg = eng.device_groups(big, 5)
+    assert [n for _, n, _ in dg] == [5, 5, 5, 5, 4] * PASS_NF and any(m for _, _, m in dg)
+    plan = eng.Plan(eng.get_device(0), PASS_GP, 0)
+    plan.set_counts(case["Mk"], case["Uk"])
+    assert plan.info["lanes_per_workgroup"] == 5
+    first, rt1, re1 = _run_and_check(plan, case, small)
+    _run_and_check(plan, case, big)
+    third, rt3, re3 = _run_and_check(plan, case, small)
+    assert all(bits_equal(a, b) for a, b in zip(first, third))
+    assert bits_equal(rt1, rt3) and bits_equal(re1, re3)
     plan.close()
 
 

@@ -37,7 +37,7 @@ OCC = 1.64  # level phase slow-down per halving of resident workgroups (see docs
 
 def lds_1lane(B, ptab_entries, scratch_entries, ct=4, kh=6, rows=1):
     """LDS of a 1-lane workgroup: `rows` score rows, the count table and its build buffers
-    (the intermediate tables only, as kp_dp_ws.h sizes them), high pairs, masks."""
+    (the intermediate tables only: the largest before the last step), high pairs, masks."""
     return rows * 4 * (B + 32) + 2 * ct * ptab_entries + 2 * 2 * ct * scratch_entries + (kh * 7 + 1) * 24 + 64
 
 

@@ -34,6 +34,8 @@
  *   kp_apply         papa.PatternPartition's checks (papa.py:53-107, with the pairwise one it
  *                    leaves commented out) and get_M_U (pattern_utils.py:192-215) for every
  *                    pattern of a partition over any table, by mask matching
+ *   kp_seq_*         nothing: the reference starts from count files and its README names an
+ *                    external tool (kmer_counter snv / background) for producing them
  */
 #ifndef KMERPAPA_HIP_H
 #define KMERPAPA_HIP_H
@@ -284,6 +286,68 @@ int kp_apply(kp_ctx *ctx, int k, const uint64_t *patterns, uint32_t n_patterns, 
 int kp_apply_host(int k, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word, const uint64_t *codes,
                   const int64_t *M, const int64_t *U, uint64_t n, int ncol, const double *rates, int32_t *pid,
                   uint64_t *pat_M, uint64_t *pat_U, double *ll, kp_apply_stats *stats);
+
+/* k-mer context counts of a genome and of its mutation sites: the two count tables every other
+ * entry point starts from.  (No reference counterpart: the reference's README names an
+ * external tool, kmer_counter, for this step; the semantics below are this project's own.)
+ * A contig is an array of bytes, one per base: A, C, G, T in either case are bases, every other
+ * byte is invalid, and a window of k positions counts only if all k bytes are bases.  The
+ * centre of the window that starts at s is position s + k/2 (io_utils._centre_window).  With
+ * fold != 0 (k must be odd) a window whose centre base is G or T is replaced by its reverse
+ * complement, so every counted k-mer has A or C in the middle.  Codes: 2 bits per letter,
+ * A = 0, C = 1, G = 2, T = 3, first letter most significant (kp_kmer_parse's); the table is
+ * dense, two columns of 4^k uint64 counters in the context's arena (the one kp_greedy and
+ * kp_apply use: neither may be called during a session, KP_E_STATE).
+ *   kp_seq_begin  k in 1..15; zeroes both columns.  KP_E_ARG: k out of range, fold with even k;
+ *                 KP_E_NOMEM: the table does not fit free device memory minus 2 GiB.
+ *   kp_seq_scan   one contig seq[n] (n < 2^32): every window whose centre lies in a region
+ *                 [reg_begin[i], reg_end[i]) adds 1 to the background column, also where its
+ *                 flanks reach outside the region; a centre whose window runs off the contig
+ *                 counts nowhere.  n_regions = 0 with null pointers = the whole contig.  Regions
+ *                 must be sorted, disjoint and within [0, n] (empty ones are fine), else
+ *                 KP_E_ARG.  n = 0 and n < k count nothing.
+ *   kp_seq_sites  the window centred at each pos[i] (0-based; pos[i] >= n is KP_E_ARG) adds 1 to
+ *                 the positive column, once per occurrence; a site whose window runs off the
+ *                 contig or holds an invalid byte is skipped and counted in the stats.
+ *   kp_seq_end    copies out 4^k counters per column (either pointer may be NULL) and ends the
+ *                 session.  Any call out of order is KP_E_STATE.
+ *   kp_seq_last_stats  figures summed over the context's current or last session.
+ * kp_seq_scan and kp_seq_sites copy the contig (n + 64 bytes), its work items (8 bytes per
+ * 8,192 centres or region) and the site positions (8 bytes each) into a second device
+ * allocation that only grows; it is not checked against the 2 GiB margin, and KP_E_NOMEM from
+ * these two calls means that allocation failed (the session stays open).
+ * With ctx = NULL the five calls run this thread's host session: the same per-base code
+ * (classify, roll the forward and reverse-complement codes, fold) serially on the host, no
+ * GPU.  kp_seq_host is one whole host session of one contig (scan != 0: the scan, of the
+ * regions or of the whole contig; then the sites).  Both exist for parity and CPU tests and
+ * are not a product path.
+ * The scan cuts the regions into work items of at most `tile` centres, one workgroup per item
+ * and step of a persistent grid.  Counters: per-workgroup uint32 LDS counters flushed with one
+ * global atomic per non-zero counter for k <= 7, global 64-bit atomics into the table above
+ * (the lanes of a wave that hold its first lane's code add once, together).
+ * Knobs, read at each call (every setting gives the same counts): KP_SEQ_GLOBAL=1 = global
+ * atomics at any k, KP_SEQ_LDS_K = largest k of the LDS path (0..7, default 7), KP_SEQ_GRID =
+ * most workgroups to launch, KP_SEQ_MERGE=0 = every lane adds on its own (measurement). */
+typedef struct {
+    uint64_t windows;         /* windows the scans counted                                     */
+    uint64_t windows_invalid; /* windows inside a contig the scans skipped for an invalid byte */
+    uint64_t sites;           /* sites counted                                                 */
+    uint64_t sites_skipped;   /* sites skipped (window off the contig or an invalid byte)      */
+    uint64_t items;           /* work items of the scans                                       */
+    double scan_ms;           /* device time of the scan kernels (HIP events; 0 on the host)   */
+    uint32_t tile;            /* centres per work item at most                                 */
+    uint32_t path;            /* of the last scan: 0 none or host, 1 LDS counters, 2 global
+                                 atomics                                                       */
+} kp_seq_stats;
+int kp_seq_begin(kp_ctx *ctx, int k, int fold);
+int kp_seq_scan(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
+                uint64_t n_regions);
+int kp_seq_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, uint64_t n_sites);
+int kp_seq_end(kp_ctx *ctx, uint64_t *pos_counts, uint64_t *bg_counts);
+int kp_seq_last_stats(kp_ctx *ctx, kp_seq_stats *out);
+int kp_seq_host(int k, int fold, const uint8_t *seq, uint64_t n, int scan, const uint64_t *reg_begin,
+                const uint64_t *reg_end, uint64_t n_regions, const uint64_t *pos, uint64_t n_sites,
+                uint64_t *pos_counts, uint64_t *bg_counts, kp_seq_stats *stats);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

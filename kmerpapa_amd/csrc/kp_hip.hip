@@ -32,6 +32,9 @@
 //   kp_apply_*       : a fitted partition applied to a count table (kp_apply.h): every row's
 //                      one-hot word against every pattern's mask word, per-pattern uint64
 //                      totals, the pairwise overlap check and the table's -2 log-likelihood
+//   kp_seq_*         : k-mer context counts of a genome and its mutation sites (kp_seq.h): a
+//                      streaming scan with a rolling window per thread and a histogram in LDS
+//                      counters (k <= 7) or global 64-bit atomics; one thread per site
 //
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
@@ -44,6 +47,7 @@
 //   kp_dump.h      parity dumps
 //   kp_math.h      kp_math_*
 //   kp_allk.h, kp_greedy.h + kp_greedy_api.h, kp_apply.h   the other scores with their drivers
+//   kp_seq.h       the sequence scan, the sites kernel and the kp_seq_* sessions
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -63,3 +67,4 @@
 #include "kp_pass.h"
 #include "kp_dump.h"
 #include "kp_math.h"
+#include "kp_seq.h"

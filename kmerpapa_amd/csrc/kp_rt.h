@@ -98,6 +98,19 @@ struct kp_arena {
     }
 };
 
+// One kp_seq_* session (kp_seq.h): the two count columns live on the device (d_tab, in the
+// context's arena) or, for the host session, in h_tab.
+struct kp_seq_sess {
+    bool active = false;
+    int k = 0, fold = 0;
+    uint64_t cells = 0;    // 4^k
+    uint64_t centres = 0;  // centres of all work items so far (windows + windows_invalid)
+    unsigned long long *d_tab = nullptr;   // [2][cells]: positive, background
+    unsigned long long *d_stat = nullptr;  // windows, sites, sites skipped
+    std::vector<uint64_t> h_tab;
+    kp_seq_stats st{};
+};
+
 #define KP_SIDE_STREAMS 3
 
 struct kp_ctx {
@@ -116,6 +129,10 @@ struct kp_ctx {
     kp_arena arena;
     std::vector<std::vector<uint64_t>> g_leaves;
     kp_greedy_stats g_stats{};  // of the last kp_greedy call
+    // kp_seq_*: the session (its table holds the arena until kp_seq_end) and a second
+    // allocation, also only grown, for the contig, its work items and the site positions
+    kp_seq_sess seq;
+    kp_arena seq_in;
 };
 
 extern "C" {
@@ -172,6 +189,7 @@ void kp_destroy(kp_ctx *c) {
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     dfree(c->arena.base);
+    dfree(c->seq_in.base);
     delete c;
 }
 

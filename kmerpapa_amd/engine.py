@@ -76,13 +76,22 @@ class KPApplyStats(ctypes.Structure):
                 ("lds_counters", ctypes.c_uint32)]
 
 
+class KPSeqStats(ctypes.Structure):
+    _fields_ = [("windows", ctypes.c_uint64), ("windows_invalid", ctypes.c_uint64), ("sites", ctypes.c_uint64),
+                ("sites_skipped", ctypes.c_uint64), ("items", ctypes.c_uint64), ("scan_ms", ctypes.c_double),
+                ("tile", ctypes.c_uint32), ("path", ctypes.c_uint32)]
+
+
+SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
+
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
            "kp_reserve_lanes", "kp_last_pass_stats", "kp_last_launch_ms", "kp_fit_leaves", "kp_dump_lane", "kp_gather_cells", "kp_fold_split",
            "kp_fold_sample", "kp_math_log", "kp_math_libm", "kp_kmer_parse", "kp_kmer_table_info", "kp_kmer_table_copy", "kp_kmer_table_free",
            "kp_format_long_rows", "kp_py_repr", "kp_device_groups", "kp_allkmers_cv", "kp_block_order_check",
            "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
-           "kp_greedy_last_stats", "kp_apply", "kp_apply_host"]
+           "kp_greedy_last_stats", "kp_apply", "kp_apply_host", "kp_seq_begin", "kp_seq_scan", "kp_seq_sites",
+           "kp_seq_end", "kp_seq_last_stats", "kp_seq_host"]
 
 
 def load():
@@ -154,6 +163,14 @@ def load():
                     vp, vp, vp, ctypes.POINTER(KPApplyStats)]
             L.kp_apply.argtypes = [vp] + tail
             L.kp_apply_host.argtypes = tail
+        if hasattr(L, "kp_seq_begin"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            L.kp_seq_begin.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+            L.kp_seq_scan.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64]
+            L.kp_seq_sites.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64]
+            L.kp_seq_end.argtypes = [vp, vp, vp]
+            L.kp_seq_last_stats.argtypes = [vp, ctypes.POINTER(KPSeqStats)]
+            L.kp_seq_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_int, vp, vp,
+                                      ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, ctypes.POINTER(KPSeqStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -408,7 +425,109 @@ def visible_devices():
     return list(range(device_count()))
 
 
-class Device:
+def _seq_bytes(seq):
+    seq = np.ascontiguousarray(seq, dtype=np.uint8).reshape(-1)
+    return seq, ctypes.c_uint64(seq.shape[0])
+
+
+class _SeqCalls:
+    """The kp_seq_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
+    calling thread's host session (:class:`HostSeq`)."""
+
+    _h = None
+
+    def seq_begin(self, k, fold=True):
+        """Open a counting session of ``k``-mers (kp_seq_begin); ``fold``: count a window whose
+        centre is G or T as its reverse complement (odd ``k`` only)."""
+        _check(load().kp_seq_begin(self._h, int(k), int(bool(fold))))
+        self._seq_cells = 4 ** int(k)
+
+    def seq_scan(self, seq, regions=None):
+        """Count every window of the contig ``seq`` (uint8, one byte per base) whose centre lies
+        in ``regions`` (``[m, 2]`` 0-based half-open, sorted and disjoint; None = the whole
+        contig) into the background column (kp_seq_scan)."""
+        seq, n = _seq_bytes(seq)
+        if regions is None:
+            _check(load().kp_seq_scan(self._h, _ptr(seq), n, None, None, ctypes.c_uint64(0)))
+            return
+        reg = np.asarray(regions, dtype=np.uint64).reshape(-1, 2)
+        if reg.shape[0] == 0:
+            return  # (no region is not "the whole contig")
+        rb, re = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1])
+        _check(load().kp_seq_scan(self._h, _ptr(seq), n, _ptr(rb), _ptr(re), ctypes.c_uint64(reg.shape[0])))
+
+    def seq_sites(self, seq, pos):
+        """Count the window centred at each 0-based position of ``pos`` on the contig ``seq``
+        into the positive column, duplicates as often as they occur (kp_seq_sites)."""
+        seq, n = _seq_bytes(seq)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        _check(load().kp_seq_sites(self._h, _ptr(seq), n, _ptr(pos), ctypes.c_uint64(pos.shape[0])))
+
+    def seq_end(self, want_pos=True, want_bg=True):
+        """Close the session (kp_seq_end).  Returns ``(pos_counts, bg_counts)``, dense uint64
+        ``[4^k]`` in code order (None for a column not wanted)."""
+        cells = getattr(self, "_seq_cells", 0)
+        pos = np.zeros(cells, np.uint64) if want_pos and cells else None
+        bg = np.zeros(cells, np.uint64) if want_bg and cells else None
+        self._seq_cells = 0
+        _check(load().kp_seq_end(self._h, _ptr(pos), _ptr(bg)))
+        return pos, bg
+
+    def seq_stats(self):
+        """Figures of the current or last session (kp_seq_last_stats) as a dict."""
+        st = KPSeqStats()
+        _check(load().kp_seq_last_stats(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSeqStats._fields_}
+
+    def seq_count(self, k, fold, jobs):
+        """One whole session.  ``jobs``: one ``(seq, regions, sites)`` per contig -- ``regions``
+        as :meth:`seq_scan` takes them, or False for no scan; ``sites`` positions or None.
+        Returns ``(pos_counts, bg_counts, stats)``."""
+        self.seq_begin(k, fold)
+        try:
+            for seq, regions, sites in jobs:
+                if regions is not False:
+                    self.seq_scan(seq, regions)
+                if sites is not None and len(sites):
+                    self.seq_sites(seq, sites)
+        except BaseException:
+            self.seq_end(False, False)
+            raise
+        pos, bg = self.seq_end()
+        return pos, bg, self.seq_stats()
+
+
+class HostSeq(_SeqCalls):
+    """The kp_seq_* calls of the calling thread's host session (ctx = NULL): the kernels' per-base
+    code run serially on the host (parity and CPU tests, not a product path)."""
+
+
+def seq_host(k, fold, jobs):
+    """:meth:`Device.seq_count` computed serially on the host."""
+    return HostSeq().seq_count(k, fold, jobs)
+
+
+def seq_host_contig(k, fold, seq, regions=None, sites=None):
+    """One host session of one contig in one call (kp_seq_host); arguments as
+    :meth:`Device.seq_count`'s jobs.  Returns ``(pos_counts, bg_counts, stats)``."""
+    seq, n = _seq_bytes(seq)
+    rb = re = None
+    nr = 0
+    scan = regions is not False
+    if scan and regions is not None:
+        reg = np.asarray(regions, dtype=np.uint64).reshape(-1, 2)
+        rb, re, nr = np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1]), reg.shape[0]
+        scan = nr > 0
+    p = np.ascontiguousarray(sites if sites is not None else [], dtype=np.uint64).reshape(-1)
+    cells = 4 ** int(k) if 1 <= int(k) <= 15 else 1
+    pos, bg = np.zeros(cells, np.uint64), np.zeros(cells, np.uint64)
+    st = KPSeqStats()
+    _check(load().kp_seq_host(int(k), int(bool(fold)), _ptr(seq), n, int(scan), _ptr(rb), _ptr(re), ctypes.c_uint64(nr),
+                              _ptr(p), ctypes.c_uint64(p.shape[0]), _ptr(pos), _ptr(bg), ctypes.byref(st)))
+    return pos, bg, {name: getattr(st, name) for name, _ in KPSeqStats._fields_}
+
+
+class Device(_SeqCalls):
     """One HIP device context (stream + events) of the library."""
 
     def __init__(self, device=0):

@@ -1,0 +1,193 @@
+"""Readers for the inputs of :mod:`kmerpapa_amd.count` (host code, numpy): genomes as FASTA or
+UCSC ``.2bit``, regions as BED, mutation sites as ``CHROM POS REF ALT`` lines.
+
+A contig is ``(name, uint8 array)``, one byte per base, exactly as the file spells it: lower-case
+soft-masking is kept, since the counting kernel reads either case, and every byte other than
+``ACGTacgt`` (``N``, IUPAC ambiguity letters) stays what it is and invalidates the windows over
+it.  The genome readers are generators, so only one contig of a genome is in memory at a time.
+"""
+import struct
+
+import numpy as np
+
+TWOBIT_MAGIC = 0x1A412743
+_COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+def _read_all(path_or_file):
+    if hasattr(path_or_file, "read"):
+        data = path_or_file.buffer.read() if hasattr(path_or_file, "buffer") else path_or_file.read()
+        return data.encode() if isinstance(data, str) else bytes(data)
+    with open(path_or_file, "rb") as f:
+        return f.read()
+
+
+def read_fasta(path_or_file):
+    """Contigs of a plain-text FASTA file: ``>`` headers (the name is the header's first word),
+    sequence lines of any length, ``\\n`` or ``\\r\\n``."""
+    data = np.frombuffer(_read_all(path_or_file), dtype=np.uint8)
+    if data.shape[0] == 0:
+        return
+    starts = np.flatnonzero(data == 10) + 1  # line starts
+    starts = np.concatenate([[0], starts[starts < data.shape[0]]])
+    heads = starts[data[starts] == ord(">")]
+    if heads.shape[0] == 0 or np.any(~np.isin(data[:heads[0]], (10, 13, 32))):
+        raise ValueError("not a FASTA file: sequence before the first '>' header")
+    ends = np.concatenate([heads[1:], [data.shape[0]]])
+    for h, e in zip(heads.tolist(), ends.tolist()):
+        nl = np.flatnonzero(data[h:e] == 10)
+        eol = h + int(nl[0]) if nl.shape[0] else e
+        words = data[h + 1:eol].tobytes().decode("ascii", errors="replace").split()
+        if not words:
+            raise ValueError("FASTA header without a name")
+        body = data[eol:e]
+        yield words[0], np.ascontiguousarray(body[(body != 10) & (body != 13)])
+
+
+_TWOBIT_LETTERS = np.frombuffer(b"TCAG", dtype=np.uint8)
+# the four letters of every packed byte, first base in the two highest bits
+_TWOBIT_LUT = _TWOBIT_LETTERS[(np.arange(256)[:, None] >> np.array([6, 4, 2, 0])[None, :]) & 3]
+
+
+def read_2bit(path):
+    """Contigs of a UCSC ``.2bit`` file, either byte order: packed bases T = 0, C = 1, A = 2,
+    G = 3, four per byte; N blocks become ``N`` bytes; mask blocks (soft-masking) are ignored,
+    so every base is upper case."""
+    with open(path, "rb") as f:
+        head = f.read(16)
+        if len(head) < 16:
+            raise ValueError("not a .2bit file: shorter than its header")
+        for order in "<>":
+            if struct.unpack(order + "I", head[:4])[0] == TWOBIT_MAGIC:
+                break
+        else:
+            raise ValueError("not a .2bit file: bad signature")
+        _, version, count, _ = struct.unpack(order + "4I", head)
+        if version != 0:
+            raise ValueError(f".2bit version {version} is not supported")
+        index = []
+        for _ in range(count):
+            size = f.read(1)[0]
+            name = f.read(size).decode("ascii")
+            index.append((name, struct.unpack(order + "I", f.read(4))[0]))
+
+        def words(n):
+            return np.frombuffer(f.read(4 * n), dtype=order + "u4").astype(np.int64)
+
+        for name, offset in index:
+            f.seek(offset)
+            dna_size, n_blocks = words(2).tolist()
+            n_starts, n_sizes = words(n_blocks), words(n_blocks)
+            mask_blocks = int(words(1)[0])
+            f.seek(8 * mask_blocks + 4, 1)  # mask starts and sizes, the reserved word
+            packed = np.frombuffer(f.read((dna_size + 3) // 4), dtype=np.uint8)
+            if packed.shape[0] != (dna_size + 3) // 4:
+                raise ValueError(f".2bit file ends inside contig {name}")
+            seq = _TWOBIT_LUT[packed].reshape(-1)[:dna_size].copy()
+            for s, length in zip(n_starts.tolist(), n_sizes.tolist()):
+                seq[s:s + length] = ord("N")
+            yield name, seq
+
+
+def is_2bit(path):
+    with open(path, "rb") as f:
+        head = f.read(4)
+    return len(head) == 4 and TWOBIT_MAGIC in (struct.unpack("<I", head)[0], struct.unpack(">I", head)[0])
+
+
+def read_genome(path):
+    """Contigs of a ``.2bit`` (by its signature) or FASTA file."""
+    return read_2bit(path) if is_2bit(path) else read_fasta(path)
+
+
+def merge_regions(regions):
+    """0-based half-open intervals ``[m, 2]`` sorted, with overlapping and adjacent ones merged
+    and empty ones dropped: no position is covered twice."""
+    reg = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    if np.any(reg < 0) or np.any(reg[:, 0] > reg[:, 1]):
+        raise ValueError("a region with a negative bound or start > end")
+    reg = reg[reg[:, 0] < reg[:, 1]]
+    if reg.shape[0] == 0:
+        return np.zeros((0, 2), np.uint64)
+    reg = reg[np.argsort(reg[:, 0], kind="stable")]
+    reach = np.maximum.accumulate(reg[:, 1])
+    first = np.concatenate([[True], reg[1:, 0] > reach[:-1]])  # starts a new merged run
+    idx = np.flatnonzero(first)
+    out = np.stack([reg[idx, 0], np.maximum.reduceat(reg[:, 1], idx)], axis=1)
+    return out.astype(np.uint64)
+
+
+def read_bed(path_or_file):
+    """``chrom start end`` lines (extra columns ignored; ``#``, ``track`` and ``browser`` lines
+    skipped) as ``{chrom: merged regions [m, 2]}``."""
+    per = {}
+    for line in _read_all(path_or_file).decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if not tok or tok[0].startswith("#") or tok[0] in ("track", "browser"):
+            continue
+        if len(tok) < 3:
+            raise ValueError(f"bad BED line:\n{line.strip()}")
+        try:
+            per.setdefault(tok[0], []).append((int(tok[1]), int(tok[2])))
+        except ValueError:
+            raise ValueError(f"bad BED line:\n{line.strip()}") from None
+    return {name: merge_regions(v) for name, v in per.items()}
+
+
+def fold_type(ref, alt):
+    """``REF>ALT`` on the strand where REF is A or C: ``G>A`` is ``C>T``."""
+    ref, alt = ref.upper(), alt.upper()
+    if ref in "GT":
+        ref, alt = _COMPLEMENT[ref], _COMPLEMENT[alt]
+    return f"{ref}>{alt}"
+
+
+def parse_type(text):
+    """A ``--type`` argument ``X>Y`` (two different bases), folded."""
+    part = text.upper().split(">")
+    if len(part) != 2 or any(len(x) != 1 or x not in _COMPLEMENT for x in part) or part[0] == part[1]:
+        raise ValueError(f"mutation type must be X>Y with two different bases of ACGT, not {text!r}")
+    return fold_type(*part)
+
+
+def read_sites(path_or_file, kind=None):
+    """``CHROM POS REF ALT`` lines (1-based POS; further columns are ignored, ``#`` lines
+    skipped; a VCF's ID column has to be cut out first).  Only single-base ``ACGT`` REF != ALT lines are
+    sites; with ``kind`` (:func:`parse_type`) only those whose folded REF>ALT equals it.
+    Returns ``({chrom: (pos0 uint64 [m], ref uint8 [m])}, stats)``, positions 0-based in file
+    order, ``stats`` counting ``lines``, ``not_snv`` and ``other_type``."""
+    per = {}
+    stats = {"lines": 0, "not_snv": 0, "other_type": 0}
+    for line in _read_all(path_or_file).decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if not tok or tok[0].startswith("#"):
+            continue
+        if len(tok) < 4:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}")
+        try:
+            pos = int(tok[1])
+        except ValueError:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}") from None
+        if pos < 1:
+            raise ValueError(f"POS is 1-based:\n{line.strip()}")
+        stats["lines"] += 1
+        ref, alt = tok[2].upper(), tok[3].upper()
+        if len(ref) != 1 or len(alt) != 1 or ref not in _COMPLEMENT or alt not in _COMPLEMENT or ref == alt:
+            stats["not_snv"] += 1
+            continue
+        if kind is not None and fold_type(ref, alt) != kind:
+            stats["other_type"] += 1
+            continue
+        pl, rl = per.setdefault(tok[0], ([], []))
+        pl.append(pos - 1)
+        rl.append(ord(ref))
+    return {name: (np.array(p, np.uint64), np.array(r, np.uint8)) for name, (p, r) in per.items()}, stats
+
+
+def match_ref(seq, pos, ref):
+    """The positions of ``pos`` that lie on the contig ``seq`` and whose base there equals
+    ``ref`` case-insensitively: ``(kept positions, n_off_contig, n_ref_mismatch)``."""
+    on = pos < np.uint64(seq.shape[0])
+    pos_on, ref_on = pos[on], ref[on]
+    same = (seq[pos_on.astype(np.intp)] & 0xDF) == ref_on
+    return pos_on[same], int((~on).sum()), int((~same).sum())

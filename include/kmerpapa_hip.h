@@ -36,6 +36,8 @@
  *                    pattern of a partition over any table, by mask matching
  *   kp_seq_*         nothing: the reference starts from count files and its README names an
  *                    external tool (kmer_counter snv / background) for producing them
+ *   kp_pred_*        nothing: taking a fitted partition's rates back to the positions and
+ *                    regions of a genome
  */
 #ifndef KMERPAPA_HIP_H
 #define KMERPAPA_HIP_H
@@ -348,6 +350,76 @@ int kp_seq_last_stats(kp_ctx *ctx, kp_seq_stats *out);
 int kp_seq_host(int k, int fold, const uint8_t *seq, uint64_t n, int scan, const uint64_t *reg_begin,
                 const uint64_t *reg_end, uint64_t n_regions, const uint64_t *pos, uint64_t n_sites,
                 uint64_t *pos_counts, uint64_t *bg_counts, kp_seq_stats *stats);
+
+/* A fitted partition taken back to the genome: per region, how many positions fall into each
+ * pattern and how many mutations the rates expect there; per position or site, which pattern.
+ * (No reference counterpart.)  Bases, windows, the centre and folding are kp_seq's above; pattern
+ * words are kp_apply's, and the window with code c belongs to pattern p when
+ * (onehot(c) & ~patterns[p]) == 0.  All results are integers, or float64 sums in a stated order,
+ * so a device session equals the host session bit for bit.
+ *   kp_pred_begin    k in 1..15; the patterns are checked as kp_apply checks them and must be
+ *                    pairwise disjoint (KP_E_ARG names the first pair that shares a k-mer), so a
+ *                    window has at most one pattern.  Builds lut[4^k] (int32: the pattern of a
+ *                    code, -1 if none) in the context's arena; KP_E_NOMEM if it does not fit free
+ *                    device memory minus 2 GiB.  The session holds the arena until kp_pred_end:
+ *                    kp_greedy, kp_apply, kp_seq_begin and kp_pred_begin during it are
+ *                    KP_E_STATE, and so is kp_pred_begin during a kp_seq session.
+ *   kp_pred_regions  one contig seq[n] (n < 2^32) and n_regions (< 2^32) half-open intervals
+ *                    within [0, n], begin <= end, in any order, overlapping or not; each is one
+ *                    output row and nothing is merged.  A region's centres are clipped to those
+ *                    whose window lies inside the contig, [k/2, n - k + k/2 + 1).
+ *                    hist[n_regions][n_patterns] (may be NULL): centres of the region whose
+ *                    window is valid and belongs to the pattern.  other[n_regions][2]: [0] centres
+ *                    with a valid window that matches no pattern, [1] centres whose window holds
+ *                    an invalid byte or runs off the contig; a row of hist and other sums to end -
+ *                    begin.  With rates[n_patterns] (may be NULL, then expected is not written)
+ *                    expected[r] = acc after acc = 0.0; for p = 0 .. n_patterns - 1: acc = acc +
+ *                    (double)hist[r][p] * rates[p] -- a product, then an add, in pattern order.
+ *                    The n_regions x n_patterns counters live in the arena during the call:
+ *                    KP_E_NOMEM if they do not fit (cut the regions into batches).
+ *   kp_pred_track    pid[end - begin] (0 <= begin <= end <= n): the pattern of the window centred
+ *                    at each position, -1 if none matches, -2 if the window holds an invalid byte
+ *                    or runs off the contig.
+ *   kp_pred_sites    the same code for the window centred at each pos[i], duplicates included;
+ *                    pos[i] >= n is KP_E_ARG.
+ *   kp_pred_end      ends the session.  Any call out of order is KP_E_STATE.
+ *   kp_pred_last_stats  figures of the context's current or last session.
+ * The contig, work items, regions and positions go into the allocation kp_seq_scan uses for them.
+ * With ctx = NULL the calls run this thread's host session: the same per-base and per-code
+ * functions serially, no GPU.  kp_pred_host is one whole host session of one contig: the regions
+ * (if n_regions), the track of [track_begin, track_end) (if track_pid is not NULL) and the sites
+ * (if n_sites).  Both exist for parity and CPU tests and are not a product path.
+ * The scan cuts every clipped region into work items of at most `tile` centres, one workgroup
+ * per item and step of a persistent grid; a window costs one 4-byte gather from lut.  Counters:
+ * uint32 LDS counters of the workgroup that belong to one item, flushed to the region's row
+ * after it with one global 64-bit atomic per non-zero counter, when n_patterns <= 16,384; else
+ * global 64-bit atomics per window.  Knobs, read at each call (every setting gives the same
+ * results): KP_PRED_GLOBAL=1 = global atomics at any size, KP_PRED_LDS_P = most patterns of the
+ * LDS path (0..16384, default 16384), KP_PRED_GRID = most workgroups to launch. */
+typedef struct {
+    uint64_t assigned;  /* centres of the regions calls that fell into a pattern              */
+    uint64_t unmatched; /* ... with a valid window that matches no pattern                    */
+    uint64_t invalid;   /* ... with an invalid byte in the window, or a window off the contig */
+    uint64_t items;     /* work items of the regions and track calls                          */
+    uint64_t lut_bytes; /* size of the lookup table                                           */
+    double lut_ms;      /* device time of the table's last build (HIP events; 0 on the host)  */
+    double scan_ms;     /* device time of the regions and track kernels (HIP events)          */
+    uint32_t tile;      /* centres per work item at most                                      */
+    uint32_t path;      /* of the last regions call: 0 none or host, 1 LDS counters, 2 global
+                           atomics                                                            */
+} kp_pred_stats;
+int kp_pred_begin(kp_ctx *ctx, int k, int fold, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word);
+int kp_pred_regions(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
+                    uint64_t n_regions, const double *rates, uint64_t *hist, uint64_t *other, double *expected);
+int kp_pred_track(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint64_t begin, uint64_t end, int32_t *pid);
+int kp_pred_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, uint64_t n_sites, int32_t *pid);
+int kp_pred_end(kp_ctx *ctx);
+int kp_pred_last_stats(kp_ctx *ctx, kp_pred_stats *out);
+int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns, uint64_t super_word,
+                 const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end, uint64_t n_regions,
+                 const double *rates, uint64_t *hist, uint64_t *other, double *expected, uint64_t track_begin,
+                 uint64_t track_end, int32_t *track_pid, const uint64_t *pos, uint64_t n_sites, int32_t *site_pid,
+                 kp_pred_stats *stats);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

@@ -35,6 +35,9 @@
 //   kp_seq_*         : k-mer context counts of a genome and its mutation sites (kp_seq.h): a
 //                      streaming scan with a rolling window per thread and a histogram in LDS
 //                      counters (k <= 7) or global 64-bit atomics; one thread per site
+//   kp_pred_*        a fitted partition taken back to the genome (kp_pred.h): a lookup table from
+//                      k-mer code to pattern, the kp_seq roll with one gather per window, and
+//                      per-region pattern histograms in LDS counters or global 64-bit atomics
 //
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
@@ -48,6 +51,7 @@
 //   kp_math.h      kp_math_*
 //   kp_allk.h, kp_greedy.h + kp_greedy_api.h, kp_apply.h   the other scores with their drivers
 //   kp_seq.h       the sequence scan, the sites kernel and the kp_seq_* sessions
+//   kp_pred.h      the prediction scan, track and sites kernels and the kp_pred_* sessions
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -68,3 +72,4 @@
 #include "kp_dump.h"
 #include "kp_math.h"
 #include "kp_seq.h"
+#include "kp_pred.h"

@@ -111,6 +111,20 @@ struct kp_seq_sess {
     kp_seq_stats st{};
 };
 
+// One kp_pred_* session (kp_pred.h): the lookup table from k-mer code to pattern index lives on
+// the device (d_lut, first in the context's arena) or, for the host session, in h_lut.  The
+// patterns are kept: growing the arena for a call's counters builds the table again.
+struct kp_pred_sess {
+    bool active = false;
+    bool lut_ok = false;  // d_lut holds the table of `pats`
+    int k = 0, fold = 0;
+    uint64_t cells = 0;  // 4^k
+    std::vector<uint64_t> pats;
+    int32_t *d_lut = nullptr;
+    std::vector<int32_t> h_lut;
+    kp_pred_stats st{};
+};
+
 #define KP_SIDE_STREAMS 3
 
 struct kp_ctx {
@@ -133,6 +147,9 @@ struct kp_ctx {
     // allocation, also only grown, for the contig, its work items and the site positions
     kp_seq_sess seq;
     kp_arena seq_in;
+    // kp_pred_*: the session (its lookup table holds the arena until kp_pred_end); the contig,
+    // work items, regions and site positions go into seq_in
+    kp_pred_sess pred;
 };
 
 extern "C" {

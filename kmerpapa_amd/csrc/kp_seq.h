@@ -222,6 +222,7 @@ extern "C" {
 int kp_seq_begin(kp_ctx *c, int k, int fold) {
     kp_seq_sess *s = seq_sess(c);
     if (s->active) return fail(KP_E_STATE, "kp_seq_begin: a session is open (kp_seq_end first)");
+    if (c && c->pred.active) return fail(KP_E_STATE, "kp_seq_begin: a kp_pred session holds the context's arena (kp_pred_end first)");
     if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, "kp_seq_begin: k must be 1..15 (a dense table of 4^k counters)");
     if (fold && k % 2 == 0) return fail(KP_E_ARG, "kp_seq_begin: strand folding needs an odd k (a centre base)");
     const uint64_t cells = 1ull << (2 * k);

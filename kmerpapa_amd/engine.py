@@ -82,7 +82,14 @@ class KPSeqStats(ctypes.Structure):
                 ("tile", ctypes.c_uint32), ("path", ctypes.c_uint32)]
 
 
+class KPPredStats(ctypes.Structure):
+    _fields_ = [("assigned", ctypes.c_uint64), ("unmatched", ctypes.c_uint64), ("invalid", ctypes.c_uint64),
+                ("items", ctypes.c_uint64), ("lut_bytes", ctypes.c_uint64), ("lut_ms", ctypes.c_double),
+                ("scan_ms", ctypes.c_double), ("tile", ctypes.c_uint32), ("path", ctypes.c_uint32)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
+PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
@@ -91,7 +98,8 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_format_long_rows", "kp_py_repr", "kp_device_groups", "kp_allkmers_cv", "kp_block_order_check",
            "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
            "kp_greedy_last_stats", "kp_apply", "kp_apply_host", "kp_seq_begin", "kp_seq_scan", "kp_seq_sites",
-           "kp_seq_end", "kp_seq_last_stats", "kp_seq_host"]
+           "kp_seq_end", "kp_seq_last_stats", "kp_seq_host", "kp_pred_begin", "kp_pred_regions", "kp_pred_track",
+           "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host"]
 
 
 def load():
@@ -171,6 +179,16 @@ def load():
             L.kp_seq_last_stats.argtypes = [vp, ctypes.POINTER(KPSeqStats)]
             L.kp_seq_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_int, vp, vp,
                                       ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, ctypes.POINTER(KPSeqStats)]
+        if hasattr(L, "kp_pred_begin"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64 = ctypes.c_uint64
+            L.kp_pred_begin.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32, u64]
+            L.kp_pred_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+            L.kp_pred_track.argtypes = [vp, vp, u64, u64, u64, vp]
+            L.kp_pred_sites.argtypes = [vp, vp, u64, vp, u64, vp]
+            L.kp_pred_end.argtypes = [vp]
+            L.kp_pred_last_stats.argtypes = [vp, ctypes.POINTER(KPPredStats)]
+            L.kp_pred_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, u64, vp, vp,
+                                       vp, vp, u64, u64, vp, vp, u64, vp, ctypes.POINTER(KPPredStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -527,7 +545,111 @@ def seq_host_contig(k, fold, seq, regions=None, sites=None):
     return pos, bg, {name: getattr(st, name) for name, _ in KPSeqStats._fields_}
 
 
-class Device(_SeqCalls):
+def _regions_arrays(regions):
+    reg = np.asarray(regions, dtype=np.uint64).reshape(-1, 2)
+    return np.ascontiguousarray(reg[:, 0]), np.ascontiguousarray(reg[:, 1]), reg.shape[0]
+
+
+class _PredCalls:
+    """The kp_pred_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
+    calling thread's host session (:class:`HostPred`)."""
+
+    _h = None
+    _pred_P = 0
+
+    def pred_begin(self, k, patterns, super_word, fold=True):
+        """Open a prediction session (kp_pred_begin): ``patterns`` are pattern words
+        (:func:`pattern_word`) that must be pairwise disjoint, ``super_word`` the super
+        pattern's; ``fold`` as :meth:`seq_begin`'s."""
+        pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+        _check(load().kp_pred_begin(self._h, int(k), int(bool(fold)), _ptr(pats), ctypes.c_uint32(pats.shape[0]),
+                                    ctypes.c_uint64(int(super_word))))
+        self._pred_P = pats.shape[0]
+
+    def pred_regions(self, seq, regions, rates=None, want_hist=True):
+        """Per region of the contig ``seq`` (``regions`` ``[m, 2]`` 0-based half-open, in any
+        order, overlapping or not): ``(hist, other, expected)`` -- ``hist`` uint64 ``[m, P]``
+        positions per pattern (None without ``want_hist``), ``other`` uint64 ``[m, 2]`` positions
+        without a pattern and positions without a valid window, ``expected`` float64 ``[m]`` the
+        sum of ``hist * rates`` in pattern order (None without ``rates``) (kp_pred_regions)."""
+        seq, n = _seq_bytes(seq)
+        rb, re, m = _regions_arrays(regions)
+        P = self._pred_P
+        r = exp = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+            if r.shape[0] != P:
+                raise ValueError("one rate per pattern")
+            exp = np.zeros(m, np.float64)
+        hist = np.zeros((m, P), np.uint64) if want_hist else None
+        other = np.zeros((m, 2), np.uint64)
+        _check(load().kp_pred_regions(self._h, _ptr(seq), n, _ptr(rb), _ptr(re), ctypes.c_uint64(m), _ptr(r), _ptr(hist),
+                                      _ptr(other), _ptr(exp)))
+        return hist, other, exp
+
+    def pred_track(self, seq, begin=0, end=None):
+        """int32 ``[end - begin]``: the pattern of the window centred at each position of
+        ``[begin, end)`` (default: the whole contig), -1 if none matches, -2 without a valid
+        window (kp_pred_track)."""
+        seq, n = _seq_bytes(seq)
+        end = seq.shape[0] if end is None else int(end)
+        pid = np.zeros(max(end - int(begin), 0), np.int32)
+        _check(load().kp_pred_track(self._h, _ptr(seq), n, ctypes.c_uint64(int(begin)), ctypes.c_uint64(end), _ptr(pid)))
+        return pid
+
+    def pred_sites(self, seq, pos):
+        """int32 ``[len(pos)]``: :meth:`pred_track`'s code at each 0-based position (kp_pred_sites)."""
+        seq, n = _seq_bytes(seq)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        pid = np.zeros(pos.shape[0], np.int32)
+        _check(load().kp_pred_sites(self._h, _ptr(seq), n, _ptr(pos), ctypes.c_uint64(pos.shape[0]), _ptr(pid)))
+        return pid
+
+    def pred_end(self):
+        """Close the session (kp_pred_end)."""
+        _check(load().kp_pred_end(self._h))
+
+    def pred_stats(self):
+        """Figures of the current or last session (kp_pred_last_stats) as a dict."""
+        st = KPPredStats()
+        _check(load().kp_pred_last_stats(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPPredStats._fields_}
+
+
+class HostPred(_PredCalls):
+    """The kp_pred_* calls of the calling thread's host session (ctx = NULL): the kernels' per-base
+    and per-code functions run serially on the host (parity and CPU tests, not a product path)."""
+
+
+def pred_host(k, patterns, super_word, fold, seq, regions=None, rates=None, track=None, sites=None):
+    """One host session of one contig in one call (kp_pred_host): the ``regions`` (with
+    ``rates``), the ``track`` range ``(begin, end)`` and the ``sites`` positions, each optional.
+    Returns ``(hist, other, expected, track_pid, site_pid, stats)``."""
+    seq, n = _seq_bytes(seq)
+    pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+    P = pats.shape[0]
+    rb, re, m = _regions_arrays(regions if regions is not None else np.zeros((0, 2)))
+    r = exp = None
+    if rates is not None:
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != P:
+            raise ValueError("one rate per pattern")
+        exp = np.zeros(m, np.float64)
+    hist, other = np.zeros((m, P), np.uint64), np.zeros((m, 2), np.uint64)
+    tb, te = (0, 0) if track is None else (int(track[0]), int(track[1]))
+    tpid = None if track is None else np.zeros(max(te - tb, 0) + 1, np.int32)  # (never a null pointer)
+    p = np.ascontiguousarray(sites if sites is not None else [], dtype=np.uint64).reshape(-1)
+    spid = np.zeros(p.shape[0], np.int32)
+    st = KPPredStats()
+    u64 = ctypes.c_uint64
+    _check(load().kp_pred_host(int(k), int(bool(fold)), _ptr(pats), ctypes.c_uint32(P), u64(int(super_word)), _ptr(seq), n,
+                               _ptr(rb), _ptr(re), u64(m), _ptr(r), _ptr(hist), _ptr(other), _ptr(exp), u64(tb), u64(te),
+                               _ptr(tpid), _ptr(p), u64(p.shape[0]), _ptr(spid), ctypes.byref(st)))
+    return (hist, other, exp, None if tpid is None else tpid[:max(te - tb, 0)], spid,
+            {name: getattr(st, name) for name, _ in KPPredStats._fields_})
+
+
+class Device(_SeqCalls, _PredCalls):
     """One HIP device context (stream + events) of the library."""
 
     def __init__(self, device=0):

@@ -38,6 +38,7 @@
  *                    external tool (kmer_counter snv / background) for producing them
  *   kp_pred_*        nothing: taking a fitted partition's rates back to the positions and
  *                    regions of a genome
+ *   kp_spec_*, kp_seq_*_typed   nothing: the same two steps for every mutation type at once
  */
 #ifndef KMERPAPA_HIP_H
 #define KMERPAPA_HIP_H
@@ -420,6 +421,93 @@ int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns,
                  const double *rates, uint64_t *hist, uint64_t *other, double *expected, uint64_t track_begin,
                  uint64_t track_end, int32_t *track_pid, const uint64_t *pos, uint64_t n_sites, int32_t *site_pid,
                  kp_pred_stats *stats);
+
+/* The whole mutation spectrum in one genome pass: counting, and a fitted partition per mutation
+ * type taken back to the genome together.  (No reference counterpart.)  Bases, windows, the centre
+ * and folding are kp_seq's above, pattern words and matching kp_apply's.
+ * Types and slots.  A window's centre base is the REF of every mutation at its centre -- after
+ * folding, if the window was replaced by its reverse complement, and then ALT is complemented too.
+ * The slot of an ALT is its rank (0..2) among the bases other than REF in ACGT order, and the type
+ * id is t = 3 * code(REF) + slot: 0..11 = A>C A>G A>T C>A C>G C>T G>A G>C G>T T>A T>C T>G; with
+ * folding only 0..5 occur.
+ * Typed counting (a kp_seq session with three positive columns, one per slot):
+ *   kp_seq_begin_typed  as kp_seq_begin; four columns of 4^k uint64 (32 GiB at k = 15) against the
+ *                       same "free minus 2 GiB" rule.
+ *   kp_seq_sites_typed  alt[i] = the ALT base of site i on the forward strand, one of ACGTacgt (any
+ *                       other byte is KP_E_ARG, checked on the host before anything is launched).  The
+ *                       window is classified, rolled and folded as kp_seq_sites does; the site adds 1
+ *                       to column slot(centre base, ALT) at the window's code.  A site whose window
+ *                       runs off the contig or holds an invalid byte, or whose ALT equals the centre
+ *                       base, is skipped and counted in sites_skipped.
+ *   kp_seq_end_typed    pos_counts[3][4^k], bg_counts[4^k] (either may be NULL); ends the session.
+ * kp_seq_scan and kp_seq_last_stats work in both kinds of session; kp_seq_sites / kp_seq_end in a
+ * typed session and kp_seq_sites_typed / kp_seq_end_typed in a plain one are KP_E_STATE.
+ * Spectrum sessions:
+ *   kp_spec_begin    k in 1..15 (fold needs an odd k); patterns[n_patterns] of every type in one
+ *                    list, ptype[p] in 0..11 (0..5 with fold) the type of pattern p; a type may have
+ *                    no pattern.  KP_E_ARG, naming the first offender: a pattern with an empty
+ *                    position or bits above position k, a type out of range, a pattern whose centre
+ *                    position (k/2) does not allow exactly the REF base of its type, two patterns
+ *                    of one type that share a k-mer, n_patterns = 0.  (Patterns of different types
+ *                    with the same slot differ in the centre, so a code has at most one pattern per
+ *                    slot.)  Builds lut[4^k] of 16-byte entries {pattern of slot 0, 1, 2, -1}, ids
+ *                    indexing `patterns`, -1 = none, in the context's arena; KP_E_NOMEM if it does
+ *                    not fit free device memory minus 2 GiB (16 GiB at k = 15).  The session holds
+ *                    the arena until kp_spec_end: kp_greedy, kp_apply, kp_seq_begin*, kp_pred_begin
+ *                    and kp_spec_begin during it are KP_E_STATE, and so is kp_spec_begin during a
+ *                    kp_seq or kp_pred session.  These exclusions hold for a device context
+ *                    only: the host sessions (ctx = NULL) of kp_seq, kp_pred and kp_spec share no
+ *                    arena and are independent of each other.
+ *   kp_spec_regions  regions as kp_pred_regions'.  hist[n_regions][n_patterns] (may be NULL).
+ *                    other[n_regions][4]: [s], s = 0..2, centres with a valid window and no pattern
+ *                    in slot s; [3] centres whose window holds an invalid byte or runs off the
+ *                    contig.  For every region and slot s the hist entries of the patterns with
+ *                    ptype % 3 == s, other[s] and other[3] sum to end - begin.  With
+ *                    rates[n_patterns] (may be NULL, then expected is not written)
+ *                    expected[r][t], t = 0..11, = acc after acc = 0.0; for p ascending with
+ *                    ptype[p] == t: acc = acc + (double)hist[r][p] * rates[p] -- a product, then an
+ *                    add; 0.0 for a type without patterns.
+ *   kp_spec_track    pid[3][end - begin], slot-major: per slot the values of kp_pred_track.
+ *   kp_spec_sites    pid[i] = the pattern in the slot of the (folded) ALT of site i, -1 if none, -2
+ *                    if the window holds an invalid byte or runs off the contig, -3 if ALT equals
+ *                    the centre base; alt and pos as kp_seq_sites_typed's.
+ *   kp_spec_end, kp_spec_last_stats  as kp_pred's; in the stats a centre counts once per slot:
+ *                    assigned + unmatched = 3 x the centres with a valid window.
+ * With ctx = NULL the calls run this thread's host session, serially with the same per-base and
+ * per-code functions; kp_spec_host is one whole host session of one contig, as kp_pred_host.
+ * The scan is kp_pred's with one 16-byte gather and up to three counter adds per valid window:
+ * uint32 LDS counters per item when n_patterns <= 16,384, global 64-bit atomics otherwise.  Knobs,
+ * read at each call (every setting gives the same results): KP_SPEC_GLOBAL, KP_SPEC_LDS_P and
+ * KP_SPEC_GRID, with the meaning of their KP_PRED_* counterparts. */
+typedef struct {
+    uint64_t assigned;  /* (centre, slot) pairs of the regions calls that fell into a pattern      */
+    uint64_t unmatched; /* ... with a valid window and no pattern in the slot                      */
+    uint64_t invalid;   /* centres with an invalid byte in the window, or a window off the contig  */
+    uint64_t items;     /* work items of the regions and track calls                               */
+    uint64_t lut_bytes; /* size of the lookup table                                                */
+    double lut_ms;      /* device time of the table's last build (HIP events; 0 on the host)       */
+    double scan_ms;     /* device time of the regions and track kernels (HIP events)               */
+    uint32_t tile;      /* centres per work item at most                                           */
+    uint32_t path;      /* of the last regions call: 0 none or host, 1 LDS counters, 2 global
+                           atomics                                                                 */
+} kp_spec_stats;
+int kp_seq_begin_typed(kp_ctx *ctx, int k, int fold);
+int kp_seq_sites_typed(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt,
+                       uint64_t n_sites);
+int kp_seq_end_typed(kp_ctx *ctx, uint64_t *pos_counts, uint64_t *bg_counts);
+int kp_spec_begin(kp_ctx *ctx, int k, int fold, const uint64_t *patterns, const uint32_t *ptype, uint32_t n_patterns);
+int kp_spec_regions(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
+                    uint64_t n_regions, const double *rates, uint64_t *hist, uint64_t *other, double *expected);
+int kp_spec_track(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint64_t begin, uint64_t end, int32_t *pid);
+int kp_spec_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt, uint64_t n_sites,
+                  int32_t *pid);
+int kp_spec_end(kp_ctx *ctx);
+int kp_spec_last_stats(kp_ctx *ctx, kp_spec_stats *out);
+int kp_spec_host(int k, int fold, const uint64_t *patterns, const uint32_t *ptype, uint32_t n_patterns, const uint8_t *seq,
+                 uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end, uint64_t n_regions, const double *rates,
+                 uint64_t *hist, uint64_t *other, double *expected, uint64_t track_begin, uint64_t track_end,
+                 int32_t *track_pid, const uint64_t *pos, const uint8_t *alt, uint64_t n_sites, int32_t *site_pid,
+                 kp_spec_stats *stats);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

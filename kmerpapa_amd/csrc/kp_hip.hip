@@ -38,6 +38,9 @@
 //   kp_pred_*        a fitted partition taken back to the genome (kp_pred.h): a lookup table from
 //                      k-mer code to pattern, the kp_seq roll with one gather per window, and
 //                      per-region pattern histograms in LDS counters or global 64-bit atomics
+//   kp_spec_*        every mutation type's partition in one pass (kp_spec.h): a table of 16-byte
+//                      entries (one pattern per ALT slot), the kp_pred roll with one gather and up
+//                      to three adds per window; typed site counting into three positive columns
 //
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
@@ -52,6 +55,8 @@
 //   kp_allk.h, kp_greedy.h + kp_greedy_api.h, kp_apply.h   the other scores with their drivers
 //   kp_seq.h       the sequence scan, the sites kernel and the kp_seq_* sessions
 //   kp_pred.h      the prediction scan, track and sites kernels and the kp_pred_* sessions
+//   kp_spec.h      the spectrum table, scan, track and sites kernels, the kp_spec_* sessions and
+//                  typed site counting
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -73,3 +78,4 @@
 #include "kp_math.h"
 #include "kp_seq.h"
 #include "kp_pred.h"
+#include "kp_spec.h"

@@ -98,14 +98,16 @@ struct kp_arena {
     }
 };
 
-// One kp_seq_* session (kp_seq.h): the two count columns live on the device (d_tab, in the
-// context's arena) or, for the host session, in h_tab.
+// One kp_seq_* session (kp_seq.h): the count columns live on the device (d_tab, in the
+// context's arena) or, for the host session, in h_tab.  A plain session has one positive column,
+// a typed one three (one per ALT slot, kp_spec.h).
 struct kp_seq_sess {
     bool active = false;
     int k = 0, fold = 0;
+    int pcols = 1;         // positive columns: 1, or 3 in a typed session
     uint64_t cells = 0;    // 4^k
     uint64_t centres = 0;  // centres of all work items so far (windows + windows_invalid)
-    unsigned long long *d_tab = nullptr;   // [2][cells]: positive, background
+    unsigned long long *d_tab = nullptr;   // [pcols + 1][cells]: positive, background
     unsigned long long *d_stat = nullptr;  // windows, sites, sites skipped
     std::vector<uint64_t> h_tab;
     kp_seq_stats st{};
@@ -123,6 +125,22 @@ struct kp_pred_sess {
     int32_t *d_lut = nullptr;
     std::vector<int32_t> h_lut;
     kp_pred_stats st{};
+};
+
+// One kp_spec_* session (kp_spec.h): as kp_pred_sess, with one pattern list for every mutation
+// type and a table of 16-byte entries {pattern of slot 0, 1, 2, -1} per k-mer code.
+struct kp_spec_sess {
+    bool active = false;
+    bool lut_ok = false;  // d_lut holds the table of `pats`
+    int k = 0, fold = 0;
+    uint64_t cells = 0;  // 4^k
+    std::vector<uint64_t> pats;
+    std::vector<uint32_t> ptype;  // [P] 0..11: 3 * code(REF) + slot
+    std::vector<uint32_t> by_type;  // [P] the pattern indices grouped by type, ascending within a type
+    uint32_t type_off[13] = {};     // by_type[type_off[t] .. type_off[t + 1]) are the patterns of type t
+    int32_t *d_lut = nullptr;     // [cells][4]
+    std::vector<int32_t> h_lut;
+    kp_spec_stats st{};
 };
 
 #define KP_SIDE_STREAMS 3
@@ -150,6 +168,8 @@ struct kp_ctx {
     // kp_pred_*: the session (its lookup table holds the arena until kp_pred_end); the contig,
     // work items, regions and site positions go into seq_in
     kp_pred_sess pred;
+    // kp_spec_*: the same for a whole mutation spectrum
+    kp_spec_sess spec;
 };
 
 extern "C" {

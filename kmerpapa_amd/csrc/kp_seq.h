@@ -217,43 +217,44 @@ static int seq_check_contig(const std::string &w, const kp_seq_sess *s, const ui
     return KP_OK;
 }
 
-extern "C" {
-
-int kp_seq_begin(kp_ctx *c, int k, int fold) {
+// kp_seq_begin (pcols = 1) and kp_seq_begin_typed (pcols = 3)
+static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols) {
     kp_seq_sess *s = seq_sess(c);
-    if (s->active) return fail(KP_E_STATE, "kp_seq_begin: a session is open (kp_seq_end first)");
-    if (c && c->pred.active) return fail(KP_E_STATE, "kp_seq_begin: a kp_pred session holds the context's arena (kp_pred_end first)");
-    if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, "kp_seq_begin: k must be 1..15 (a dense table of 4^k counters)");
-    if (fold && k % 2 == 0) return fail(KP_E_ARG, "kp_seq_begin: strand folding needs an odd k (a centre base)");
-    const uint64_t cells = 1ull << (2 * k);
+    if (s->active) return fail(KP_E_STATE, w + ": a session is open (kp_seq_end first)");
+    if (c && c->pred.active) return fail(KP_E_STATE, w + ": a kp_pred session holds the context's arena (kp_pred_end first)");
+    if (c && c->spec.active) return fail(KP_E_STATE, w + ": a kp_spec session holds the context's arena (kp_spec_end first)");
+    if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, w + ": k must be 1..15 (a dense table of 4^k counters)");
+    if (fold && k % 2 == 0) return fail(KP_E_ARG, w + ": strand folding needs an odd k (a centre base)");
+    const uint64_t cells = 1ull << (2 * k), cols = (uint64_t)pcols + 1;
     if (c) {
         KP_HIP(hipSetDevice(c->device));
-        const size_t need = g_up(2 * cells * 8) + g_up(64);
+        const size_t need = g_up(cols * cells * 8) + g_up(64);
         if (need > c->arena.bytes) {
             size_t fr = 0, tot = 0;
             KP_HIP(hipMemGetInfo(&fr, &tot));
             if (need + (2ull << 30) > fr + c->arena.bytes)
-                return fail(KP_E_NOMEM, "kp_seq_begin: the table of " + std::to_string(k) + "-mers needs " +
+                return fail(KP_E_NOMEM, w + ": the table of " + std::to_string(k) + "-mers needs " +
                                             std::to_string(need >> 20) + " MiB of device memory, " +
                                             std::to_string((fr + c->arena.bytes) >> 20) + " MiB are free (2 GiB stay free)");
         }
-        int rc = c->arena.reserve("kp_seq_begin", need);
+        int rc = c->arena.reserve(w.c_str(), need);
         if (rc) return rc;
-        s->d_tab = (unsigned long long *)c->arena.take(2 * cells * 8);
+        s->d_tab = (unsigned long long *)c->arena.take(cols * cells * 8);
         s->d_stat = (unsigned long long *)c->arena.take(64);
-        if ((rc = c->arena.check("kp_seq_begin"))) return rc;
-        KP_HIP(hipMemsetAsync(s->d_tab, 0, 2 * cells * 8, c->stream));
+        if ((rc = c->arena.check(w.c_str()))) return rc;
+        KP_HIP(hipMemsetAsync(s->d_tab, 0, cols * cells * 8, c->stream));
         KP_HIP(hipMemsetAsync(s->d_stat, 0, 64, c->stream));
         KP_HIP(hipStreamSynchronize(c->stream));
     } else {
         try {
-            s->h_tab.assign(2 * cells, 0);
+            s->h_tab.assign(cols * cells, 0);
         } catch (const std::bad_alloc &) {
-            return fail(KP_E_NOMEM, "kp_seq_begin: the host table of " + std::to_string(k) + "-mers does not fit memory");
+            return fail(KP_E_NOMEM, w + ": the host table of " + std::to_string(k) + "-mers does not fit memory");
         }
     }
     s->k = k;
     s->fold = fold ? 1 : 0;
+    s->pcols = pcols;
     s->cells = cells;
     s->centres = 0;
     s->st = kp_seq_stats{};
@@ -261,6 +262,33 @@ int kp_seq_begin(kp_ctx *c, int k, int fold) {
     s->active = true;
     return KP_OK;
 }
+
+// kp_seq_end (pcols = 1) and kp_seq_end_typed (pcols = 3): pos_counts holds pcols columns
+static int seq_end(const std::string &w, kp_ctx *c, int pcols, uint64_t *pos_counts, uint64_t *bg_counts) {
+    kp_seq_sess *s = seq_sess(c);
+    if (!s->active) return fail(KP_E_STATE, w + ": no session (kp_seq_begin first)");
+    if (s->pcols != pcols)
+        return fail(KP_E_STATE, w + (pcols == 1 ? ": the session is typed (kp_seq_end_typed)" : ": the session is not typed (kp_seq_end)"));
+    s->active = false;  // whatever happens below, the session is over
+    const size_t bytes = (size_t)s->cells * 8;
+    if (c) {
+        KP_HIP(hipSetDevice(c->device));
+        if (pos_counts) KP_HIP(hipMemcpyAsync(pos_counts, s->d_tab, pcols * bytes, hipMemcpyDeviceToHost, c->stream));
+        if (bg_counts) KP_HIP(hipMemcpyAsync(bg_counts, s->d_tab + pcols * s->cells, bytes, hipMemcpyDeviceToHost, c->stream));
+        KP_HIP(hipStreamSynchronize(c->stream));
+    } else {
+        if (pos_counts) memcpy(pos_counts, s->h_tab.data(), pcols * bytes);
+        if (bg_counts) memcpy(bg_counts, s->h_tab.data() + pcols * s->cells, bytes);
+        std::vector<uint64_t>().swap(s->h_tab);
+    }
+    return KP_OK;
+}
+
+extern "C" {
+
+int kp_seq_begin(kp_ctx *c, int k, int fold) { return seq_begin("kp_seq_begin", c, k, fold, 1); }
+
+int kp_seq_begin_typed(kp_ctx *c, int k, int fold) { return seq_begin("kp_seq_begin_typed", c, k, fold, 3); }
 
 int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
                 uint64_t n_regions) {
@@ -277,7 +305,7 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
     const std::vector<kp_s_item> items = seq_items(n, k, reg_begin, reg_end, n_regions, &centres);
     if (!c) {
         const uint32_t mask = (uint32_t)(s->cells - 1);
-        uint64_t *bg = s->h_tab.data() + s->cells;
+        uint64_t *bg = s->h_tab.data() + (uint64_t)s->pcols * s->cells;
         for (const kp_s_item &it : items) {
             kp_s_win w{0u, 0u, 0u};
             const uint64_t b0 = (uint64_t)it.first - (uint64_t)(k / 2);
@@ -319,7 +347,7 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
         A.k = k;
         A.fold = s->fold;
         A.cells = (uint32_t)s->cells;
-        A.tab = s->d_tab + s->cells;
+        A.tab = s->d_tab + (uint64_t)s->pcols * s->cells;
         A.stat = s->d_stat;
         KP_HIP(hipEventRecord(c->ev[0], st));
         if (lds)
@@ -349,6 +377,7 @@ int kp_seq_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos,
     kp_seq_sess *s = seq_sess(c);
     int rc = seq_check_contig("kp_seq_sites", s, seq, n);
     if (rc) return rc;
+    if (s->pcols != 1) return fail(KP_E_STATE, "kp_seq_sites: the session is typed (kp_seq_sites_typed)");
     if (n_sites && !pos) return fail(KP_E_ARG, "kp_seq_sites: null positions");
     if (n_sites >= (1ull << 39)) return fail(KP_E_ARG, "kp_seq_sites: 2^39 sites or more in one call");
     for (uint64_t i = 0; i < n_sites; ++i)
@@ -393,21 +422,11 @@ int kp_seq_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos,
 }
 
 int kp_seq_end(kp_ctx *c, uint64_t *pos_counts, uint64_t *bg_counts) {
-    kp_seq_sess *s = seq_sess(c);
-    if (!s->active) return fail(KP_E_STATE, "kp_seq_end: no session (kp_seq_begin first)");
-    s->active = false;  // whatever happens below, the session is over
-    const size_t bytes = (size_t)s->cells * 8;
-    if (c) {
-        KP_HIP(hipSetDevice(c->device));
-        if (pos_counts) KP_HIP(hipMemcpyAsync(pos_counts, s->d_tab, bytes, hipMemcpyDeviceToHost, c->stream));
-        if (bg_counts) KP_HIP(hipMemcpyAsync(bg_counts, s->d_tab + s->cells, bytes, hipMemcpyDeviceToHost, c->stream));
-        KP_HIP(hipStreamSynchronize(c->stream));
-    } else {
-        if (pos_counts) memcpy(pos_counts, s->h_tab.data(), bytes);
-        if (bg_counts) memcpy(bg_counts, s->h_tab.data() + s->cells, bytes);
-        std::vector<uint64_t>().swap(s->h_tab);
-    }
-    return KP_OK;
+    return seq_end("kp_seq_end", c, 1, pos_counts, bg_counts);
+}
+
+int kp_seq_end_typed(kp_ctx *c, uint64_t *pos_counts, uint64_t *bg_counts) {
+    return seq_end("kp_seq_end_typed", c, 3, pos_counts, bg_counts);
 }
 
 int kp_seq_last_stats(kp_ctx *c, kp_seq_stats *out) {

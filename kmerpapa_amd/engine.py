@@ -88,8 +88,13 @@ class KPPredStats(ctypes.Structure):
                 ("scan_ms", ctypes.c_double), ("tile", ctypes.c_uint32), ("path", ctypes.c_uint32)]
 
 
+class KPSpecStats(ctypes.Structure):
+    _fields_ = list(KPPredStats._fields_)
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
+SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
 
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
@@ -99,7 +104,9 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
            "kp_greedy_last_stats", "kp_apply", "kp_apply_host", "kp_seq_begin", "kp_seq_scan", "kp_seq_sites",
            "kp_seq_end", "kp_seq_last_stats", "kp_seq_host", "kp_pred_begin", "kp_pred_regions", "kp_pred_track",
-           "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host"]
+           "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
+           "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
+           "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host"]
 
 
 def load():
@@ -189,6 +196,19 @@ def load():
             L.kp_pred_last_stats.argtypes = [vp, ctypes.POINTER(KPPredStats)]
             L.kp_pred_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, u64, vp, vp,
                                        vp, vp, u64, u64, vp, vp, u64, vp, ctypes.POINTER(KPPredStats)]
+        if hasattr(L, "kp_spec_begin"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64 = ctypes.c_uint64
+            L.kp_seq_begin_typed.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+            L.kp_seq_sites_typed.argtypes = [vp, vp, u64, vp, vp, u64]
+            L.kp_seq_end_typed.argtypes = [vp, vp, vp]
+            L.kp_spec_begin.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint32]
+            L.kp_spec_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+            L.kp_spec_track.argtypes = [vp, vp, u64, u64, u64, vp]
+            L.kp_spec_sites.argtypes = [vp, vp, u64, vp, vp, u64, vp]
+            L.kp_spec_end.argtypes = [vp]
+            L.kp_spec_last_stats.argtypes = [vp, ctypes.POINTER(KPSpecStats)]
+            L.kp_spec_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint32, vp, u64, vp, vp, u64, vp, vp, vp,
+                                       vp, u64, u64, vp, vp, vp, u64, vp, ctypes.POINTER(KPSpecStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -448,6 +468,15 @@ def _seq_bytes(seq):
     return seq, ctypes.c_uint64(seq.shape[0])
 
 
+def _alt_bytes(alt, n):
+    if isinstance(alt, (bytes, bytearray, str)):
+        alt = np.frombuffer(alt.encode("latin-1") if isinstance(alt, str) else bytes(alt), np.uint8)
+    alt = np.ascontiguousarray(alt, dtype=np.uint8).reshape(-1)
+    if alt.shape[0] != n:
+        raise ValueError("one ALT base per position")
+    return alt
+
+
 class _SeqCalls:
     """The kp_seq_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
     calling thread's host session (:class:`HostSeq`)."""
@@ -490,6 +519,47 @@ class _SeqCalls:
         self._seq_cells = 0
         _check(load().kp_seq_end(self._h, _ptr(pos), _ptr(bg)))
         return pos, bg
+
+    def seq_begin_typed(self, k, fold=True):
+        """Open a typed counting session (kp_seq_begin_typed): three positive columns, one per ALT
+        slot (:func:`kmerpapa_amd.spectrum.slot_of`), beside the background column."""
+        _check(load().kp_seq_begin_typed(self._h, int(k), int(bool(fold))))
+        self._seq_cells = 4 ** int(k)
+
+    def seq_sites_typed(self, seq, pos, alt):
+        """Count the window centred at each 0-based position of ``pos`` into the column of its ALT
+        base ``alt`` (bytes ``ACGTacgt`` on the forward strand) (kp_seq_sites_typed)."""
+        seq, n = _seq_bytes(seq)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        alt = _alt_bytes(alt, pos.shape[0])
+        _check(load().kp_seq_sites_typed(self._h, _ptr(seq), n, _ptr(pos), _ptr(alt), ctypes.c_uint64(pos.shape[0])))
+
+    def seq_end_typed(self, want_pos=True, want_bg=True):
+        """Close a typed session (kp_seq_end_typed).  Returns ``(pos_counts [3, 4^k], bg_counts
+        [4^k])``, dense uint64 in code order (None for what is not wanted)."""
+        cells = getattr(self, "_seq_cells", 0)
+        pos = np.zeros((3, cells), np.uint64) if want_pos and cells else None
+        bg = np.zeros(cells, np.uint64) if want_bg and cells else None
+        self._seq_cells = 0
+        _check(load().kp_seq_end_typed(self._h, _ptr(pos), _ptr(bg)))
+        return pos, bg
+
+    def seq_count_typed(self, k, fold, jobs):
+        """One whole typed session.  ``jobs``: one ``(seq, regions, sites)`` per contig as
+        :meth:`seq_count`'s, ``sites`` being ``(pos, alt)`` or None.  Returns ``(pos_counts,
+        bg_counts, stats)``."""
+        self.seq_begin_typed(k, fold)
+        try:
+            for seq, regions, sites in jobs:
+                if regions is not False:
+                    self.seq_scan(seq, regions)
+                if sites is not None and len(sites[0]):
+                    self.seq_sites_typed(seq, *sites)
+        except BaseException:
+            self.seq_end_typed(False, False)
+            raise
+        pos, bg = self.seq_end_typed()
+        return pos, bg, self.seq_stats()
 
     def seq_stats(self):
         """Figures of the current or last session (kp_seq_last_stats) as a dict."""
@@ -649,7 +719,115 @@ def pred_host(k, patterns, super_word, fold, seq, regions=None, rates=None, trac
             {name: getattr(st, name) for name, _ in KPPredStats._fields_})
 
 
-class Device(_SeqCalls, _PredCalls):
+class _SpecCalls:
+    """The kp_spec_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
+    calling thread's host session (:class:`HostSpec`)."""
+
+    _h = None
+    _spec_P = 0
+
+    def spec_begin(self, k, patterns, ptype, fold=True):
+        """Open a spectrum session (kp_spec_begin): ``patterns`` are the pattern words of every
+        mutation type in one list, ``ptype`` their type ids (0..11, 0..5 with ``fold``); the
+        patterns of one type must be pairwise disjoint."""
+        pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+        ty = np.asarray(ptype, dtype=np.int64).reshape(-1)
+        if ty.shape[0] != pats.shape[0]:
+            raise ValueError("one type per pattern")
+        if np.any(ty < 0) or np.any(ty >= 1 << 32):
+            raise ValueError("a type id that is no uint32")
+        ty = np.ascontiguousarray(ty, dtype=np.uint32)
+        _check(load().kp_spec_begin(self._h, int(k), int(bool(fold)), _ptr(pats), _ptr(ty), ctypes.c_uint32(pats.shape[0])))
+        self._spec_P = pats.shape[0]
+
+    def spec_regions(self, seq, regions, rates=None, want_hist=True):
+        """Per region of the contig ``seq``: ``(hist, other, expected)`` -- ``hist`` uint64 ``[m,
+        P]`` (None without ``want_hist``), ``other`` uint64 ``[m, 4]`` positions without a
+        pattern in slot 0, 1, 2 and positions without a valid window, ``expected`` float64 ``[m,
+        12]`` per type id (None without ``rates``) (kp_spec_regions)."""
+        seq, n = _seq_bytes(seq)
+        rb, re, m = _regions_arrays(regions)
+        P = self._spec_P
+        r = exp = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+            if r.shape[0] != P:
+                raise ValueError("one rate per pattern")
+            exp = np.zeros((m, 12), np.float64)
+        hist = np.zeros((m, P), np.uint64) if want_hist else None
+        other = np.zeros((m, 4), np.uint64)
+        _check(load().kp_spec_regions(self._h, _ptr(seq), n, _ptr(rb), _ptr(re), ctypes.c_uint64(m), _ptr(r), _ptr(hist),
+                                      _ptr(other), _ptr(exp)))
+        return hist, other, exp
+
+    def spec_track(self, seq, begin=0, end=None):
+        """int32 ``[3, end - begin]``: per ALT slot the pattern of the window centred at each
+        position, -1 if none, -2 without a valid window (kp_spec_track)."""
+        seq, n = _seq_bytes(seq)
+        end = seq.shape[0] if end is None else int(end)
+        pid = np.zeros((3, max(end - int(begin), 0)), np.int32)
+        _check(load().kp_spec_track(self._h, _ptr(seq), n, ctypes.c_uint64(int(begin)), ctypes.c_uint64(end), _ptr(pid)))
+        return pid
+
+    def spec_sites(self, seq, pos, alt):
+        """int32 ``[len(pos)]``: the pattern in the slot of each site's (folded) ALT, -1 if none,
+        -2 without a valid window, -3 where ALT equals the centre base (kp_spec_sites)."""
+        seq, n = _seq_bytes(seq)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        alt = _alt_bytes(alt, pos.shape[0])
+        pid = np.zeros(pos.shape[0], np.int32)
+        _check(load().kp_spec_sites(self._h, _ptr(seq), n, _ptr(pos), _ptr(alt), ctypes.c_uint64(pos.shape[0]), _ptr(pid)))
+        return pid
+
+    def spec_end(self):
+        """Close the session (kp_spec_end)."""
+        _check(load().kp_spec_end(self._h))
+
+    def spec_stats(self):
+        """Figures of the current or last session (kp_spec_last_stats) as a dict."""
+        st = KPSpecStats()
+        _check(load().kp_spec_last_stats(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSpecStats._fields_}
+
+
+class HostSpec(_SpecCalls, _SeqCalls):
+    """The kp_spec_* (and typed kp_seq_*) calls of the calling thread's host session (ctx = NULL):
+    the kernels' per-base and per-code functions run serially on the host (parity and CPU tests,
+    not a product path)."""
+
+
+def spec_host(k, patterns, ptype, fold, seq, regions=None, rates=None, track=None, sites=None):
+    """One host session of one contig in one call (kp_spec_host): the ``regions`` (with
+    ``rates``), the ``track`` range ``(begin, end)`` and the ``sites`` ``(pos, alt)``, each
+    optional.  Returns ``(hist, other, expected, track_pid, site_pid, stats)``."""
+    seq, n = _seq_bytes(seq)
+    pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+    ty = np.ascontiguousarray(ptype, dtype=np.uint32).reshape(-1)
+    P = pats.shape[0]
+    rb, re, m = _regions_arrays(regions if regions is not None else np.zeros((0, 2)))
+    r = exp = None
+    if rates is not None:
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != P:
+            raise ValueError("one rate per pattern")
+        exp = np.zeros((m, 12), np.float64)
+    hist, other = np.zeros((m, P), np.uint64), np.zeros((m, 4), np.uint64)
+    tb, te = (0, 0) if track is None else (int(track[0]), int(track[1]))
+    tlen = max(te - tb, 0)
+    tpid = None if track is None else np.zeros(3 * tlen + 1, np.int32)  # (never a null pointer)
+    p = np.ascontiguousarray(sites[0] if sites is not None else [], dtype=np.uint64).reshape(-1)
+    a = _alt_bytes(sites[1] if sites is not None else b"", p.shape[0])
+    spid = np.zeros(p.shape[0], np.int32)
+    st = KPSpecStats()
+    u64 = ctypes.c_uint64
+    _check(load().kp_spec_host(int(k), int(bool(fold)), _ptr(pats), _ptr(ty), ctypes.c_uint32(P), _ptr(seq), n, _ptr(rb),
+                               _ptr(re), u64(m), _ptr(r), _ptr(hist), _ptr(other), _ptr(exp), u64(tb), u64(te), _ptr(tpid),
+                               _ptr(p), _ptr(a), u64(p.shape[0]), _ptr(spid), ctypes.byref(st)))
+    return (hist, other, exp, None if tpid is None else tpid[:3 * tlen].reshape(3, tlen), spid,
+            {name: getattr(st, name) for name, _ in KPSpecStats._fields_})
+
+
+class Device(_SeqCalls, _PredCalls, _SpecCalls):
     """One HIP device context (stream + events) of the library."""
 
     def __init__(self, device=0):

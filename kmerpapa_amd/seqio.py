@@ -184,6 +184,39 @@ def read_sites(path_or_file, kind=None):
     return {name: (np.array(p, np.uint64), np.array(r, np.uint8)) for name, (p, r) in per.items()}, stats
 
 
+def read_sites_alt(path_or_file):
+    """:func:`read_sites` without a type filter that also returns ALT: ``({chrom: (pos0 uint64
+    [m], ref uint8 [m], alt uint8 [m])}, stats)``, upper-case bytes, positions in file order.
+    ``stats`` counts ``lines``, ``not_snv`` and, of those, ``alt_equals_ref``: the lines whose REF
+    and ALT are the same single base."""
+    per = {}
+    stats = {"lines": 0, "not_snv": 0, "alt_equals_ref": 0}
+    for line in _read_all(path_or_file).decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if not tok or tok[0].startswith("#"):
+            continue
+        if len(tok) < 4:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}")
+        try:
+            pos = int(tok[1])
+        except ValueError:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}") from None
+        if pos < 1:
+            raise ValueError(f"POS is 1-based:\n{line.strip()}")
+        stats["lines"] += 1
+        ref, alt = tok[2].upper(), tok[3].upper()
+        if len(ref) != 1 or len(alt) != 1 or ref not in _COMPLEMENT or alt not in _COMPLEMENT or ref == alt:
+            stats["not_snv"] += 1
+            stats["alt_equals_ref"] += len(ref) == 1 and ref == alt and ref in _COMPLEMENT
+            continue
+        pl, rl, al = per.setdefault(tok[0], ([], [], []))
+        pl.append(pos - 1)
+        rl.append(ord(ref))
+        al.append(ord(alt))
+    return {name: (np.array(p, np.uint64), np.array(r, np.uint8), np.array(a, np.uint8))
+            for name, (p, r, a) in per.items()}, stats
+
+
 def match_ref(seq, pos, ref):
     """The positions of ``pos`` that lie on the contig ``seq`` and whose base there equals
     ``ref`` case-insensitively: ``(kept positions, n_off_contig, n_ref_mismatch)``."""

@@ -1,0 +1,695 @@
+"""The whole mutation spectrum in one genome pass: ``python -m kmerpapa_amd.spectrum`` (the
+``kmerpapa-spectrum`` command).
+
+A mutation-rate model is one partition per mutation type -- after strand folding ``A>C A>G A>T C>A
+C>G C>T``, each fitted under its own super pattern (``NNANN``, ``NNCNN``).  ``kmerpapa-count``,
+``kmerpapa`` and ``kmerpapa-predict`` handle one type per run; this module counts every type's
+sites in one session (``engine.Device.seq_*_typed``), joins the per-type partitions into one model
+file and takes the whole model back to the genome in one scan (``engine.Device.spec_*``,
+kp_spec.h): a window's centre base is the (folded) REF, an ALT is one of the three other bases, and
+its rank among them in ``ACGT`` order is its *slot*, so three slots per k-mer cover every type and
+the type id is ``3 * code(REF) + slot``.  Semantics: include/kmerpapa_hip.h.  The reference has no
+such step.
+
+The model file is this project's own format: a header ``type pattern p_neg p_pos p_rate`` and one
+row per pattern, grouped by type in id order, the patterns of a type in the order of its partition
+file, rates as Python float reprs.
+
+``track`` without ``--type`` writes, per position, the sum of the rates of the model's types with
+the position's (folded) REF base, added in slot order from 0.0 -- the probability that the position
+mutates at all.  A position gets a value only if every one of those types has a pattern for its
+window (and the model has at least one such type): a partly covered position has no value.
+"""
+import argparse
+import contextlib
+import gc
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+from . import seqio
+from .apply import read_partition
+from .predict import DEFAULT_BUDGET, _bed_lines, _by_contig, _region_array, _site_lines
+
+BASES = "ACGT"
+HEADER = ["type", "pattern", "p_neg", "p_pos", "p_rate"]
+ALT_IS_REF = -3
+
+
+def TYPES(fold=True):
+    """The canonical type strings in id order: 6 with strand folding, 12 without."""
+    return [f"{r}>{a}" for r in (BASES[:2] if fold else BASES) for a in BASES if a != r]
+
+
+def type_id(text, fold=True):
+    """The id of ``X>Y``: ``3 * code(REF) + slot``.  With ``fold`` the type is folded first as
+    ``seqio.fold_type`` does (``G>A`` is ``C>T``)."""
+    kind = seqio.parse_type(text)  # (validates; folded)
+    if not fold:
+        kind = text.upper()
+    return TYPES(False).index(kind)
+
+
+def slot_of(ref, alt):
+    """The rank of ``alt`` among the bases other than ``ref`` in ``ACGT`` order."""
+    return [b for b in BASES if b != ref.upper()].index(alt.upper())
+
+
+def super_pattern(kind, k):
+    """The super pattern a type is fitted under: N everywhere, REF in the centre."""
+    return "N" * (k // 2) + kind[0] + "N" * (k - 1 - k // 2)
+
+
+class Model:
+    """One partition per mutation type.  ``types``: the type strings present, in id order;
+    ``names``, ``ptype`` (type ids, uint32), ``rates`` (float64) and ``counts`` (``(M, U)``): one
+    entry per pattern, grouped by type; ``k`` the pattern length."""
+
+    def __init__(self, names, ptype, rates, counts=None):
+        self.names = list(names)
+        self.ptype = np.asarray(ptype, np.uint32).reshape(-1)
+        self.rates = np.asarray(rates, np.float64).reshape(-1)
+        self.counts = [tuple(c) for c in counts] if counts is not None else [(0, 0)] * len(self.names)
+        if not self.names:
+            raise ValueError("a model without patterns")
+        if not len(self.names) == self.ptype.shape[0] == self.rates.shape[0] == len(self.counts):
+            raise ValueError("one type, rate and pair of counts per pattern")
+        self.k = len(self.names[0])
+        if any(len(x) != self.k for x in self.names):
+            raise ValueError("patterns of different lengths")
+        if np.any(self.ptype >= 12) or np.any(np.diff(self.ptype.astype(np.int64)) < 0):
+            raise ValueError("the patterns must be grouped by type in id order")
+        all_types = TYPES(False)
+        self.types = [all_types[t] for t in sorted(set(self.ptype.tolist()))]
+
+    @property
+    def folded(self):
+        """Every type has A or C as REF: the model can be used with strand folding."""
+        return bool(np.all(self.ptype < 6))
+
+    @classmethod
+    def from_partitions(cls, parts):
+        """``parts``: ``{type string: (names, counts, rates)}`` as ``apply.read_partition``
+        returns them.  Types as written (not folded); a type may be given once."""
+        names, ptype, rates, counts = [], [], [], []
+        ids = {}
+        for kind, part in parts.items():
+            t = type_id(kind, fold=False)
+            if t in ids:
+                raise ValueError(f"type {kind} given twice")
+            ids[t] = part
+        for t in sorted(ids):
+            pn, pc, pr = ids[t]
+            names += list(pn)
+            counts += list(pc)
+            rates += list(pr)
+            ptype += [t] * len(pn)
+        return cls(names, ptype, rates, counts)
+
+    @classmethod
+    def read(cls, file):
+        if isinstance(file, (str, os.PathLike)):
+            with open(file) as f:
+                return cls.read(f)
+        if file.readline().split() != HEADER:
+            raise ValueError(f"not a spectrum model: the first line must be '{' '.join(HEADER)}'")
+        names, ptype, rates, counts = [], [], [], []
+        for line in file:
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) != 5:
+                raise ValueError(f"bad line in the model file:\n{line.strip()}")
+            ptype.append(type_id(tok[0], fold=False))
+            names.append(tok[1])
+            counts.append((int(tok[3]), int(tok[2])))
+            rates.append(float(tok[4]))
+        return cls(names, ptype, rates, counts)
+
+    def write(self, file):
+        if isinstance(file, (str, os.PathLike)):
+            with open(file, "w") as f:
+                return self.write(f)
+        all_types = TYPES(False)
+        file.write(" ".join(HEADER) + "\n")
+        file.write("".join(f"{all_types[t]} {x} {u} {m} {float(r)!r}\n"
+                           for t, x, (m, u), r in zip(self.ptype.tolist(), self.names, self.counts, self.rates.tolist())))
+
+    def words(self):
+        from .engine import pattern_word
+        return [pattern_word(x) for x in self.names]
+
+
+def _check_fold(model, fold):
+    if not 1 <= model.k <= 15:
+        raise ValueError("the patterns must be 1..15 positions long")
+    if fold and model.k % 2 == 0:
+        raise ValueError("strand folding needs an odd k (use --no-fold)")
+    if fold and not model.folded:
+        raise ValueError("the model has types with REF G or T: it was not fitted with strand folding (use --no-fold)")
+
+
+@contextlib.contextmanager
+def session(model, fold=True, host=False):
+    """A kp_spec session of ``model``: yields the object whose ``spec_regions`` / ``spec_track`` /
+    ``spec_sites`` / ``spec_stats`` run in it -- the first visible GPU's ``engine.Device``, or
+    with ``host=True`` the host session."""
+    from . import engine
+    _check_fold(model, fold)
+    s = engine.HostSpec() if host else engine.get_device(engine.visible_devices()[0])
+    s.spec_begin(model.k, model.words(), model.ptype, fold)
+    try:
+        yield s
+    finally:
+        s.spec_end()
+
+
+def count_genome(contigs, k, fold=True, regions=None, sites=None, host=False):
+    """``count.count_genome`` for every mutation type at once.  ``sites``: ``{name: (pos0, alt)}``,
+    ``alt`` the ALT bases as bytes.  Returns ``(pos_counts [3, 4^k], bg_counts [4^k], stats)``:
+    column = slot of the (folded) ALT."""
+    from . import engine
+
+    def jobs():
+        for name, seq in contigs:
+            if regions is None:
+                reg = None
+            elif regions is False or name not in regions:
+                reg = False
+            else:
+                reg = seqio.merge_regions(regions[name])
+                reg = reg if reg.shape[0] else False
+            st = sites.get(name) if sites is not None else None
+            if reg is not False or (st is not None and len(st[0])):
+                yield seq, reg, st
+
+    s = engine.HostSpec() if host else engine.get_device(engine.visible_devices()[0])
+    return s.seq_count_typed(k, fold, jobs())
+
+
+def type_column(k, pos_counts, kind):
+    """The dense positive column of one type: its slot's column at the k-mers with its REF in
+    the centre, zero elsewhere."""
+    ref, slot = BASES.index(kind[0]), slot_of(kind[0], kind[2])
+    centre = (np.arange(4 ** k, dtype=np.uint64) >> np.uint64(2 * (k - 1 - k // 2))) & np.uint64(3)
+    return np.where(centre == ref, pos_counts[slot], 0).astype(np.uint64)
+
+
+def tables_of(k, fold, pos_counts, bg_counts):
+    """``{type: KmerCounts}`` of typed counts: rows = the k-mers with the type's REF in the centre
+    and a non-zero background, M the type's column, U = background - M (``count.table_of``'s
+    ``ValueError`` where M > background)."""
+    from .count import table_of
+    out = {}
+    for kind in TYPES(fold):
+        col = type_column(k, pos_counts, kind)
+        bg = type_column(k, np.stack([bg_counts] * 3), kind)
+        out[kind] = table_of(k, col, bg)
+    return out
+
+
+def count_tables(contigs, k, fold=True, regions=None, sites=None, host=False):
+    """:func:`count_genome` as one ``io_utils.KmerCounts`` per type (:func:`tables_of`)."""
+    pos, bg, _ = count_genome(contigs, k, fold, regions, sites, host)
+    return tables_of(k, fold, pos, bg)
+
+
+def _contig_regions(s, seq, reg, P, rates, want_hist, budget):
+    """One contig's regions in batches of at most ``budget`` counters a call."""
+    m = reg.shape[0]
+    step = max(1, int(budget) // max(P, 1))
+    hist = np.zeros((m, P), np.uint64) if want_hist else None
+    other = np.zeros((m, 4), np.uint64)
+    exp = np.zeros((m, 12), np.float64)
+    for b in range(0, m, step):
+        h, o, e = s.spec_regions(seq, reg[b:b + step], rates, want_hist)
+        other[b:b + step], exp[b:b + step] = o, e
+        if want_hist:
+            hist[b:b + step] = h
+    return hist, other, exp
+
+
+def region_rates(contigs, model, regions, fold=True, want_hist=False, host=False, budget=DEFAULT_BUDGET):
+    """The model over regions of ``contigs`` (``predict.region_counts`` for every type at once).
+    Returns ``{contig: (hist, other, expected)}``: ``hist`` uint64 ``[m, P]`` (None without
+    ``want_hist``), ``other`` uint64 ``[m, 4]`` = positions without a pattern in slot 0, 1, 2 and
+    positions without a valid window, ``expected`` float64 ``[m, 12]`` by type id.  Batching by
+    ``budget`` counters a call changes no result."""
+    out = {}
+    with session(model, fold, host) as s:
+        for name, seq in contigs:
+            if name in regions:
+                out[name] = _contig_regions(s, seq, _region_array(regions[name]), len(model.names), model.rates,
+                                            want_hist, budget)
+    return out
+
+
+def track(seq_or_contigs, model, fold=True, host=False, begin=0, end=None):
+    """The pattern index per ALT slot at every position: int32 ``[3, len]`` (``predict.track``'s
+    codes per slot).  One contig (with ``begin`` / ``end`` a range of it) or an iterable of
+    ``(name, array)`` giving a dict."""
+    with session(model, fold, host) as s:
+        if isinstance(seq_or_contigs, (np.ndarray, bytes, bytearray)):
+            seq = np.frombuffer(seq_or_contigs, np.uint8) if not isinstance(seq_or_contigs, np.ndarray) else seq_or_contigs
+            return s.spec_track(seq, begin, end)
+        return {name: s.spec_track(seq) for name, seq in seq_or_contigs}
+
+
+def site_rates(contigs, model, sites, fold=True, host=False):
+    """The pattern of each site's own mutation type: ``sites`` is ``{contig: (pos0, alt)}``, the
+    result ``{contig: int32 array}`` (-1 none, -2 no valid window, -3 ALT equals the centre base);
+    ``predict.rates_of(pid, model.rates)`` gives the rates."""
+    out = {}
+    with session(model, fold, host) as s:
+        for name, seq in contigs:
+            if name in sites:
+                out[name] = s.spec_sites(seq, *sites[name])
+    return out
+
+
+_CLASS = np.full(256, 4, np.uint8)
+for _i, _b in enumerate(BASES):
+    _CLASS[ord(_b)] = _CLASS[ord(_b.lower())] = _i
+
+
+def folded_ref(seq, fold):
+    """The REF code (0..3; 4 = no base) of every position on the counted strand."""
+    ref = _CLASS[seq]
+    return np.where(fold & (ref >= 2) & (ref < 4), 3 - ref, ref).astype(np.uint8)
+
+
+def track_values(model, pid, ref, kind=None):
+    """``(has, value)`` per position of a track ``pid [3, len]`` with ``ref`` =
+    :func:`folded_ref` of the same positions: one type's rate, or by default the sum over the
+    model's types with that REF in slot order (the module docstring's rule)."""
+    rates = np.concatenate([model.rates, [0.0]])
+    present = np.zeros((5, 3), bool)
+    for t in set(model.ptype.tolist()):
+        if kind is None or t == type_id(kind, fold=False):
+            present[t // 3, t % 3] = True
+    pres = present[ref].T  # [3, len]
+    has = pres.any(axis=0) & np.all(~pres | (pid >= 0), axis=0)
+    value = np.zeros(pid.shape[1], np.float64)
+    for s in range(3):
+        value = value + np.where(pres[s] & has, rates[np.where(pid[s] >= 0, pid[s], -1)], 0.0)
+    return has, value
+
+
+# ---------------------------------------------------------------------------
+# the command line
+# ---------------------------------------------------------------------------
+
+def _type_file(prefix, kind):
+    return f"{prefix}.{kind[0]}_{kind[2]}.txt"
+
+
+def _matched_sites(path, report):
+    """The sites file per contig (``seqio.read_sites_alt``), its line counts added to ``report``."""
+    raw, st = seqio.read_sites_alt(path)
+    report.update(st)
+    report.update(off_contig=0, ref_mismatch=0)
+    return raw
+
+
+def _keep_matching(seq, pos, ref, alt, report):
+    on = pos < np.uint64(seq.shape[0])
+    same = np.zeros(pos.shape[0], bool)
+    same[on] = (seq[pos[on].astype(np.intp)] & 0xDF) == ref[on]
+    report["off_contig"] += int((~on).sum())
+    report["ref_mismatch"] += int((on & ~same).sum())
+    return pos[same], ref[same], alt[same]
+
+
+def _run_count(args, k, fold, host, report):
+    from .count import write_counts
+    raw = _matched_sites(args.sites, report)
+    regions = seqio.read_bed(args.bed) if args.bed else None
+    seen, kept = set(), {}
+
+    def contigs():
+        for name, seq in seqio.read_genome(args.genome):
+            seen.add(name)
+            if name in raw:
+                pos, ref, alt = _keep_matching(seq, *raw[name], report)
+                kept[name] = (pos, alt)
+            yield name, seq
+
+    pos, bg, st = count_genome(contigs(), k, fold, regions=regions, sites=kept, host=host)
+    report["unknown_contig"] = sum(len(v[0]) for name, v in raw.items() if name not in seen)
+    if regions is not None:
+        report["unknown_contig_regions"] = sum(len(v) for name, v in regions.items() if name not in seen)
+    report.update(windows=st["windows"], windows_invalid=st["windows_invalid"], sites=st["sites"],
+                  sites_skipped=st["sites_skipped"])
+    with open(f"{args.output}.background.txt", "w") as out:
+        write_counts(out, k, bg)
+    written = {}  # type: (sites counted, background windows with its REF in the centre)
+    for kind in TYPES(fold):
+        col = type_column(k, pos, kind)
+        if col.any():
+            with open(_type_file(args.output, kind), "w") as out:
+                write_counts(out, k, col)
+            written[kind] = (int(col.sum()), int(type_column(k, np.stack([bg] * 3), kind).sum()))
+    return written
+
+
+def _run_join(pairs, output):
+    parts = {}
+    for item in pairs:
+        kind, _, path = item.partition("=")
+        if not path:
+            raise ValueError(f"--type takes X>Y=PARTITION_FILE, not {item!r}")
+        with open(path) as f:
+            parts[kind.upper()] = read_partition(f)
+        if not parts[kind.upper()][0]:
+            raise ValueError(f"the partition file {path} holds no pattern")
+    model = Model.from_partitions(parts)
+    for t, x in zip(model.ptype.tolist(), model.names):
+        if x[model.k // 2] != BASES[t // 3]:
+            raise ValueError(f"pattern {x} of type {TYPES(False)[t]} does not have its REF base in the centre")
+    model.write(output)
+    return model
+
+
+def _run_fit(args, k, fold, host, report):
+    from . import cli
+    tmp = None
+    prefix = args.prefix
+    if prefix is None:
+        tmp = tempfile.TemporaryDirectory()
+        prefix = os.path.join(tmp.name, "counts")
+    try:
+        args.output, model_path = prefix, args.output
+        kinds = _run_count(args, k, fold, host, report)
+        if not kinds:
+            raise ValueError("no site was counted")
+        pairs = []
+        for kind in kinds:
+            part = f"{prefix}.{kind[0]}_{kind[2]}.partition.txt"
+            argv = ["-p", _type_file(prefix, kind), "-b", f"{prefix}.background.txt", "-s", super_pattern(kind, k),
+                    "-o", part, "--verbosity", str(args.verbosity)]
+            if args.penalty_values:
+                argv += ["-c"] + [repr(x) for x in args.penalty_values]
+            if args.pseudo_counts:
+                argv += ["-a"] + [repr(x) for x in args.pseudo_counts]
+            if args.nfolds is not None:
+                argv += ["-N", str(args.nfolds)]
+            if args.seed is not None:
+                argv += ["--seed", str(args.seed)]
+            argv += ["--greedy"] * args.greedy + ["--greedyCV"] * args.greedyCV
+            rc = cli.main(argv)
+            gc.collect()  # (cli.main leaves its output file to be closed with its argparse namespace)
+            if rc:
+                raise ValueError(f"the fit of {kind} failed with exit code {rc}")
+            pairs.append(f"{kind}={part}")
+        model = _run_join(pairs, model_path)
+        # a partition file read before it was written out in full would be short: every type's
+        # pattern counts must add up to the count files the fit read
+        for kind, (n_pos, n_bg) in kinds.items():
+            own = [c for c, t in zip(model.counts, model.ptype.tolist()) if t == type_id(kind, fold=False)]
+            got = (sum(m for m, _ in own), sum(m + u for m, u in own))
+            if got != (n_pos, n_bg):
+                raise RuntimeError(f"the partition of {kind} holds {got[0]} sites in {got[1]} windows, its count files "
+                                   f"{n_pos} in {n_bg}: the partition file is incomplete")
+        report["types"] = len(model.types)
+        report["patterns"] = len(model.names)
+    finally:
+        if tmp is not None:
+            tmp.cleanup()
+
+
+def _observed(path, genome_contigs, model, fold, report):
+    """Per contig ``{type id: sorted positions}`` of the sites whose REF matches the genome, for
+    the model's types; the sites of other types are counted in ``report["observed_other_type"]``."""
+    raw = _matched_sites(path, report)
+    out = {}
+    ids = np.array([[3 * r + (a if a < r else a - 1) if a != r else 0 for a in range(4)] for r in range(4)])
+    for name, seq in genome_contigs.items():
+        if name not in raw:
+            continue
+        pos, ref, alt = _keep_matching(seq, *raw[name], report)
+        r, a = _CLASS[ref].astype(np.int64), _CLASS[alt].astype(np.int64)
+        if fold:
+            flip = r >= 2
+            r, a = np.where(flip, 3 - r, r), np.where(flip, 3 - a, a)
+        t = ids[r, a]
+        out[name] = {int(x): np.sort(pos[t == x]) for x in set(model.ptype.tolist())}
+        report["observed_other_type"] = report.get("observed_other_type", 0) + int((~np.isin(t, model.ptype)).sum())
+    report["unknown_contig"] = sum(len(v[0]) for name, v in raw.items() if name not in genome_contigs)
+    return out
+
+
+def _run_regions(args, model, fold, host, report, out):
+    rows = _bed_lines(args.bed)
+    per = _by_contig(rows)
+    n = len(rows)
+    tids = sorted(set(model.ptype.tolist()))
+    other = np.zeros((n, 4), np.uint64)
+    exp = np.zeros((n, 12), np.float64)
+    obs = np.zeros((n, 12), np.int64)
+    seen = {}
+    with session(model, fold, host) as s:
+        for name, seq in seqio.read_genome(args.genome):
+            if name in per:
+                seen[name] = seq
+                idx = np.array(per[name])
+                reg = np.array([(rows[i][1], rows[i][2]) for i in per[name]], np.uint64)
+                _, o, e = _contig_regions(s, seq, reg, len(model.names), model.rates, False, DEFAULT_BUDGET)
+                other[idx], exp[idx] = o, e
+        st = s.spec_stats()
+    report.update(assigned=st["assigned"], unmatched=st["unmatched"], invalid=st["invalid"],
+                  unknown_contig_regions=sum(len(v) for name, v in per.items() if name not in seen))
+    if args.observed:
+        sites = _observed(args.observed, seen, model, fold, report)
+        for name, by_type in sites.items():
+            idx = np.array(per[name])
+            reg = np.array([(rows[i][1], rows[i][2]) for i in per[name]], np.uint64)
+            for t, pos in by_type.items():
+                obs[idx, t] = np.searchsorted(pos, reg[:, 1], "left") - np.searchsorted(pos, reg[:, 0], "left")
+    labelled = any(row[3] is not None for row in rows)
+    kinds = [TYPES(False)[t] for t in tids]
+    head = ["#chrom", "start", "end"] + ["name"] * labelled + ["valid", "invalid", "exp_total"] + [f"exp_{x}" for x in kinds]
+    if args.observed:
+        head += ["obs_total"] + [f"obs_{x}" for x in kinds]
+    lines = [" ".join(head) + "\n"]
+    for i, (chrom, b, e, label) in enumerate(rows):
+        known = chrom in seen
+        inv = int(other[i, 3])
+        tok = [chrom, str(b), str(e)] + [label if label is not None else "."] * labelled
+        tok += [str(e - b - inv if known else 0), str(inv)]
+        total = 0.0
+        for t in tids:
+            total = total + float(exp[i, t])
+        tok += [repr(total)] + [repr(float(exp[i, t])) for t in tids]
+        if args.observed:
+            tok += [str(int(obs[i, tids].sum()))] + [str(int(obs[i, t])) for t in tids]
+        lines.append(" ".join(tok) + "\n")
+    out.write("".join(lines))
+
+
+def _run_track(args, model, fold, host, report, out):
+    regions = seqio.read_bed(args.bed) if args.bed else None
+    kind = None
+    if args.type:
+        kind = TYPES(False)[type_id(args.type, fold)]
+        if kind not in model.types:
+            raise ValueError(f"the model has no type {kind}")
+    seen = set()
+    positions = 0
+    with session(model, fold, host) as s:
+        for name, seq in seqio.read_genome(args.genome):
+            seen.add(name)
+            if regions is None:
+                ranges = [(0, seq.shape[0])]
+            else:
+                ranges = regions.get(name, np.zeros((0, 2), np.uint64)).tolist()
+            for b, e in ranges:
+                if e > seq.shape[0]:
+                    raise ValueError(f"region {name} {b} {e} ends past the contig's {seq.shape[0]} bases")
+                pid = s.spec_track(seq, b, e)
+                if not pid.shape[1]:
+                    continue
+                has, value = track_values(model, pid, folded_ref(seq[b:e], fold), kind)
+                key = np.where(has, value.view(np.int64), -1)
+                first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))  # where a run starts
+                last = np.concatenate([first[1:], [key.shape[0]]])
+                keep = has[first]
+                positions += int((last - first)[keep].sum())
+                out.write("".join(f"{name} {b + x} {b + y} {v!r}\n" for x, y, v in
+                                  zip(first[keep].tolist(), last[keep].tolist(), value[first][keep].tolist())))
+    report["positions_with_a_rate"] = positions
+    if regions is not None:
+        report["unknown_contig_regions"] = sum(len(v) for name, v in regions.items() if name not in seen)
+
+
+def _run_sites(args, model, fold, host, report, out):
+    rows, skipped = _site_lines(args.sites)
+    per = _by_contig(rows)
+    pid = np.full(len(rows), -4, np.int32)  # -4: not looked up
+    report.update(lines=len(rows) + skipped, not_snv=skipped, off_contig=0, ref_mismatch=0)
+    seen = set()
+    with session(model, fold, host) as s:
+        for name, seq in seqio.read_genome(args.genome):
+            if name in per:
+                seen.add(name)
+                idx = np.array(per[name])
+                pos = np.array([rows[i][1] - 1 for i in per[name]], np.uint64)
+                ref = np.array([ord(rows[i][2].upper()) for i in per[name]], np.uint8)
+                alt = np.array([ord(rows[i][3].upper()) for i in per[name]], np.uint8)
+                on = pos < np.uint64(seq.shape[0])
+                same = np.zeros(pos.shape[0], bool)
+                same[on] = (seq[pos[on].astype(np.intp)] & 0xDF) == ref[on]
+                report["off_contig"] += int((~on).sum())
+                report["ref_mismatch"] += int((on & ~same).sum())
+                pid[idx[same]] = s.spec_sites(seq, pos[same], alt[same])
+    report["unknown_contig"] = sum(len(v) for name, v in per.items() if name not in seen)
+    report["without_pattern"] = int(((pid == -1) | (pid == -2)).sum())
+    kinds = TYPES(False)
+    rates = model.rates.tolist()
+    out.write("".join(f"{c} {p} {r} {a} " + (f"{kinds[int(model.ptype[j])]} {model.names[j]} {rates[j]!r}\n" if j >= 0
+                                             else "NA NA NA\n")
+                      for (c, p, r, a), j in zip(rows, pid.tolist())))
+
+
+def get_parser():
+    p = argparse.ArgumentParser(prog="kmerpapa-spectrum",
+                                description="Counts, fits and applies one k-mer pattern partition per mutation type "
+                                            "in one pass over the genome")
+    sub = p.add_subparsers(dest="command", required=True)
+
+    def common(q, output_help, default=None):
+        q.add_argument("--no-fold", action="store_true",
+                       help="Take every window as read (12 types); default: a window with G or T in the centre is "
+                            "taken as its reverse complement and ALT is complemented with it (6 types)")
+        q.add_argument("-o", "--output", metavar="PATH", help=output_help, default=default, required=default is None)
+        q.add_argument("--verbosity", type=int, default=1,
+                       help="Amount of info printed to stderr during execution. 0:silent, 1:default")
+
+    def counting(q):
+        q.add_argument("genome", help="Genome as FASTA (plain text) or UCSC .2bit")
+        q.add_argument("sites", help="File of CHROM POS REF ALT lines, POS 1-based")
+        size = q.add_mutually_exclusive_group(required=True)
+        size.add_argument("-k", type=int, help="Length of the k-mers (1..15; odd unless --no-fold)")
+        size.add_argument("--radius", type=int, help="Bases on each side of the centre: k = 2 * radius + 1")
+        q.add_argument("--bed", metavar="FILE", help="Count the background only where the centre lies in these regions")
+
+    cnt = sub.add_parser("count", help="background counts and the counts of every mutation type's sites, in one session")
+    counting(cnt)
+    common(cnt, "Prefix of PREFIX.background.txt and one PREFIX.X_Y.txt per type that has sites")
+    joi = sub.add_parser("join", help="per-type partition files into one model file")
+    joi.add_argument("--type", action="append", required=True, metavar="X>Y=FILE",
+                     help="A type and the output table of kmerpapa (short or -l format) fitted for it; repeat per type")
+    joi.add_argument("-o", "--output", required=True, metavar="MODEL", help="The model file")
+    joi.add_argument("--verbosity", type=int, default=1)
+    fit = sub.add_parser("fit", help="count, fit every type that has sites with kmerpapa's options, and join")
+    counting(fit)
+    common(fit, "The model file")
+    fit.add_argument("--prefix", metavar="PREFIX", help="Keep the count and partition files under this prefix")
+    fit.add_argument("-c", "--penalty_values", type=float, nargs="+", metavar="c")
+    fit.add_argument("-a", "--pseudo_counts", type=float, nargs="+", metavar="a")
+    fit.add_argument("-N", "--nfolds", type=int, metavar="N")
+    fit.add_argument("--seed", type=int)
+    fit.add_argument("--greedy", action="store_true")
+    fit.add_argument("--greedyCV", action="store_true")
+
+    def applying(q):
+        q.add_argument("genome", help="Genome as FASTA (plain text) or UCSC .2bit")
+        q.add_argument("--model", required=True, metavar="FILE", help="Model file of `join` or `fit`")
+        common(q, "Output file (default: standard output)", "-")
+
+    reg = sub.add_parser("regions", help="per region: expected mutations by type and in total, and the observed ones")
+    applying(reg)
+    reg.add_argument("--bed", metavar="FILE", required=True, help="The regions; a 4th column is carried through as a name")
+    reg.add_argument("--observed", metavar="SITES", help="CHROM POS REF ALT lines to count per region and type.  Only sites of the model's types are "
+                          "counted (obs_total is their sum); the number of the others is reported on stderr as "
+                          "observed_other_type")
+    trk = sub.add_parser("track", help="the rate at every position, as bedGraph")
+    applying(trk)
+    trk.add_argument("--bed", metavar="FILE", help="Only the positions of these regions")
+    trk.add_argument("--type", metavar="X>Y",
+                     help="This type's rate.  Default: the sum of the rates of the model's types with the position's "
+                          "REF base, in slot order; a position where one of them has no pattern gets no value")
+    sit = sub.add_parser("sites", help="the type, pattern and rate of given mutations")
+    applying(sit)
+    sit.add_argument("sites", help="File of CHROM POS REF ALT lines, POS 1-based")
+    return p
+
+
+def _overlap_report(model):
+    """Pairs of patterns of one type that share k-mers."""
+    from .apply import lca_pattern
+    from .engine import apply_host, pattern_word
+    pairs = 0
+    for t in sorted(set(model.ptype.tolist())):
+        names = [x for x, y in zip(model.names, model.ptype.tolist()) if y == t]
+        pairs += apply_host(model.k, [pattern_word(x) for x in names], pattern_word(lca_pattern(names)), [], [], [])[4][
+            "overlap_pairs"]
+    return pairs
+
+
+def main(argv=None, host=False):
+    """Run the program.  Exit code 0; 1 with a message if a type's patterns overlap; 2 on input
+    errors."""
+    import io
+
+    from .engine import KPError
+    args = get_parser().parse_args(args=argv)
+    report = {}
+    buf = io.StringIO()
+    try:
+        if args.command == "join":
+            _run_join(args.type, args.output)
+            return 0
+        fold = not args.no_fold
+        seqio.is_2bit(args.genome)  # (a genome that cannot be opened is reported before a GPU is touched)
+        if args.command in ("count", "fit"):
+            k = args.k if args.k is not None else 2 * args.radius + 1
+            if not 1 <= k <= 15:
+                raise ValueError("k must be 1..15")
+            if fold and k % 2 == 0:
+                raise ValueError("strand folding needs an odd k (use --no-fold)")
+            (_run_count if args.command == "count" else _run_fit)(args, k, fold, host, report)
+        else:
+            model = Model.read(args.model)
+            _check_fold(model, fold)
+            run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites}[args.command]
+            try:
+                if args.command == "track" and args.output != "-":
+                    with open(args.output, "w") as out:  # (a genome's track is written contig by contig)
+                        run(args, model, fold, host, report, out)
+                else:
+                    run(args, model, fold, host, report, sys.stdout if args.command == "track" else buf)
+            except KPError as e:
+                if e.code == -1 and "not a partition" in str(e):
+                    print(f"kmerpapa-spectrum: a type's patterns are not a partition: {_overlap_report(model)} pairs of "
+                          "patterns share k-mers", file=sys.stderr)
+                    return 1
+                raise
+    except (ValueError, OSError, KeyError, KPError) as e:
+        if isinstance(e, KPError) and e.code != -1:  # only KP_E_ARG is the input's fault
+            raise
+        print(f"kmerpapa-spectrum: input error: {e}", file=sys.stderr)
+        return 2
+    if args.verbosity > 0:
+        for key, v in report.items():
+            print(f"{key}={v}", file=sys.stderr)
+    if args.command in ("count", "fit"):
+        return 0
+    try:
+        if args.command == "track":
+            sys.stdout.flush()
+        elif args.output == "-":
+            sys.stdout.write(buf.getvalue())
+            sys.stdout.flush()
+        else:
+            with open(args.output, "w") as out:
+                out.write(buf.getvalue())
+    except OSError as e:
+        print(f"kmerpapa-spectrum: cannot write the output: {e}", file=sys.stderr)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -478,7 +478,57 @@ int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns,
  * The scan is kp_pred's with one 16-byte gather and up to three counter adds per valid window:
  * uint32 LDS counters per item when n_patterns <= 16,384, global 64-bit atomics otherwise.  Knobs,
  * read at each call (every setting gives the same results): KP_SPEC_GLOBAL, KP_SPEC_LDS_P and
- * KP_SPEC_GRID, with the meaning of their KP_PRED_* counterparts. */
+ * KP_SPEC_GRID, with the meaning of their KP_PRED_* counterparts.
+ * Simulation (a call of a spectrum session): a random mutation set drawn from the model.
+ *   kp_spec_simulate  Per position of the regions: the window, its validity, centre and folding
+ *                    are kp_spec_regions'; an invalid window, or one that runs off the contig, draws
+ *                    nothing.  A valid window with code c reads lut[c] = {id0, id1, id2, -1};
+ *                    r_s = id_s >= 0 ? rates[id_s] * scale : 0.0 (a product); c0 = r0, c1 = c0 + r1,
+ *                    c2 = c1 + r2 (adds in that order, no contraction).  With the uniform number u
+ *                    below the position mutates into slot 0 if u < c0, else slot 1 if u < c1, else
+ *                    slot 2 if u < c2, else not at all: at most one mutation per position, each
+ *                    type's marginal probability exactly its rate.  (Where c2 == 0.0 the generator
+ *                    may be skipped: the result is the same.)  The slots are those of the counted
+ *                    (folded) strand; the reported ALT is on the forward strand -- if the window
+ *                    was replaced by its reverse complement the slot's base is complemented back --
+ *                    as upper-case ASCII.
+ *                    u: Philox4x32 with 10 rounds, key (seed low 32 bits, seed high 32 bits),
+ *                    counter (position low 32, position high 32, contig_id, replicate), position =
+ *                    the 0-based position in the contig.  One round on counter (c0, c1, c2, c3) and
+ *                    key (k0, k1): p0 = 0xD2511F53 * c0 and p1 = 0xCD9E8D57 * c2 as 64-bit products;
+ *                    the new counter is (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0)); then
+ *                    k0 += 0x9E3779B9, k1 += 0xBB67AE85 mod 2^32.  With the output x0..x3,
+ *                    u = (double)(((uint64)x1 << 32 | x0) >> 11) * 2^-53, both steps exact.  (The
+ *                    published Random123 known answers hold: the all-zero counter and key give
+ *                    6627e8d5 e169c58d bc57ac4c 9b00dbd8.)  The draw depends on (seed, contig_id,
+ *                    position, replicate) and the model only -- not on the regions asked for, the
+ *                    grid, knobs or arrival order -- and the device result equals the host result
+ *                    bit for bit.
+ *                    Regions are clipped as kp_spec_regions clips them and must be ascending and
+ *                    disjoint (reg_begin[i] >= reg_end[i - 1], begin <= end; empty and adjacent
+ *                    regions are fine).  *n_hits is always the total number of hits.  out_pos,
+ *                    out_alt and out_pid (the pattern whose rate produced the hit) receive the hits
+ *                    in ascending position order only if *n_hits <= cap; otherwise they are left
+ *                    untouched and the call still returns KP_OK: the caller repeats it with a
+ *                    larger cap, and the repeat is exact by construction.  KP_E_STATE outside a
+ *                    session.  KP_E_ARG, checked on the host before any launch and naming the first
+ *                    offender: a rate or scale that is not finite or is negative; a REF base for
+ *                    which the sum over its three types of the type's largest rates[p] * scale
+ *                    exceeds 1.0; unsorted or overlapping regions.
+ *   kp_spec_last_sim  figures of the session's last kp_spec_simulate call.
+ * With ctx = NULL the draw runs serially in the host session with the same functions.  On the
+ * device it is an ordered two-pass compaction: a count kernel (the scan's roll and gathers, the
+ * draw, one plain store of the item's hits), an exclusive scan of the items' hits whose total is
+ * read back (the call ends there if it exceeds cap), and a write kernel that draws again and puts
+ * each hit at item offset + thread offset + rank; the order never depends on atomics.  Knob, read at
+ * each call (every setting gives the same results): KP_SIM_GRID caps the grid. */
+typedef struct {
+    uint64_t windows; /* valid windows inside the regions                                          */
+    uint64_t hits;    /* mutations drawn                                                           */
+    uint64_t items;   /* work items                                                                */
+    double count_ms;  /* device time of the count and offsets kernels (HIP events; 0 on the host)  */
+    double write_ms;  /* device time of the write kernel (HIP events; 0 on the host or if not run) */
+} kp_spec_sim_stats;
 typedef struct {
     uint64_t assigned;  /* (centre, slot) pairs of the regions calls that fell into a pattern      */
     uint64_t unmatched; /* ... with a valid window and no pattern in the slot                      */
@@ -508,6 +558,11 @@ int kp_spec_host(int k, int fold, const uint64_t *patterns, const uint32_t *ptyp
                  uint64_t *hist, uint64_t *other, double *expected, uint64_t track_begin, uint64_t track_end,
                  int32_t *track_pid, const uint64_t *pos, const uint8_t *alt, uint64_t n_sites, int32_t *site_pid,
                  kp_spec_stats *stats);
+int kp_spec_simulate(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig_id, const uint64_t *reg_begin,
+                     const uint64_t *reg_end, uint64_t n_regions, const double *rates, double scale, uint64_t seed,
+                     uint32_t replicate, uint64_t cap, uint64_t *out_pos, uint8_t *out_alt, int32_t *out_pid,
+                     uint64_t *n_hits);
+int kp_spec_last_sim(kp_ctx *ctx, kp_spec_sim_stats *out);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

@@ -41,6 +41,9 @@
 //   kp_spec_*        every mutation type's partition in one pass (kp_spec.h): a table of 16-byte
 //                      entries (one pattern per ALT slot), the kp_pred roll with one gather and up
 //                      to three adds per window; typed site counting into three positive columns
+//   kp_sim_*         a random mutation set drawn from a spectrum model (kp_sim.h): the kp_spec roll,
+//                      one counter-based random number per position and an ordered two-pass
+//                      compaction of the hits
 //
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
@@ -57,6 +60,8 @@
 //   kp_pred.h      the prediction scan, track and sites kernels and the kp_pred_* sessions
 //   kp_spec.h      the spectrum table, scan, track and sites kernels, the kp_spec_* sessions and
 //                  typed site counting
+//   kp_sim.h       the draw of a mutation set from a spectrum model: Philox per position, the count,
+//                  offsets and write kernels and kp_spec_simulate
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -79,3 +84,4 @@
 #include "kp_seq.h"
 #include "kp_pred.h"
 #include "kp_spec.h"
+#include "kp_sim.h"

@@ -141,6 +141,7 @@ struct kp_spec_sess {
     int32_t *d_lut = nullptr;     // [cells][4]
     std::vector<int32_t> h_lut;
     kp_spec_stats st{};
+    kp_spec_sim_stats sim{};  // of the last kp_spec_simulate call (kp_sim.h)
 };
 
 #define KP_SIDE_STREAMS 3

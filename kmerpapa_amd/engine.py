@@ -92,6 +92,11 @@ class KPSpecStats(ctypes.Structure):
     _fields_ = list(KPPredStats._fields_)
 
 
+class KPSpecSimStats(ctypes.Structure):
+    _fields_ = [("windows", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("items", ctypes.c_uint64),
+                ("count_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
@@ -106,7 +111,7 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_seq_end", "kp_seq_last_stats", "kp_seq_host", "kp_pred_begin", "kp_pred_regions", "kp_pred_track",
            "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
            "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
-           "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host"]
+           "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim"]
 
 
 def load():
@@ -209,6 +214,11 @@ def load():
             L.kp_spec_last_stats.argtypes = [vp, ctypes.POINTER(KPSpecStats)]
             L.kp_spec_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint32, vp, u64, vp, vp, u64, vp, vp, vp,
                                        vp, u64, u64, vp, vp, vp, u64, vp, ctypes.POINTER(KPSpecStats)]
+        if hasattr(L, "kp_spec_simulate"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            L.kp_spec_simulate.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, ctypes.c_double, u64, u32, u64, vp, vp, vp,
+                                           u64p]
+            L.kp_spec_last_sim.argtypes = [vp, ctypes.POINTER(KPSpecSimStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -778,6 +788,47 @@ class _SpecCalls:
         pid = np.zeros(pos.shape[0], np.int32)
         _check(load().kp_spec_sites(self._h, _ptr(seq), n, _ptr(pos), _ptr(alt), ctypes.c_uint64(pos.shape[0]), _ptr(pid)))
         return pid
+
+    def spec_simulate(self, seq, regions, rates, seed, contig_id=0, replicate=0, scale=1.0, cap=None):
+        """A random mutation set of the contig ``seq`` drawn from the session's model with the
+        pattern ``rates`` times ``scale`` (kp_spec_simulate): ``(pos uint64, alt uint8, pid
+        int32)`` in ascending position order, ``alt`` the forward-strand ALT as upper-case ASCII,
+        ``pid`` the pattern whose rate produced the hit.  ``regions`` must be ascending and
+        disjoint.  The draw depends on ``(seed, contig_id, position, replicate)`` and the model
+        only.  ``cap``: room for the first try (default: the largest expectation the rates allow
+        plus six standard deviations); a set that does not fit is drawn again with its own size."""
+        seq, n = _seq_bytes(seq)
+        rb, re, m = _regions_arrays(regions)
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != self._spec_P:
+            raise ValueError("one rate per pattern")
+        for name, v in (("seed", seed), ("contig_id", contig_id), ("replicate", replicate)):
+            if not 0 <= int(v) < (1 << 64 if name == "seed" else 1 << 32):
+                raise ValueError(f"{name} must be an unsigned {64 if name == 'seed' else 32}-bit integer")
+        if cap is None:
+            span = float((re - rb).sum()) if m and np.all(re >= rb) else 0.0
+            top = float(r.max()) * float(scale) if r.shape[0] else 0.0
+            mean = span * min(max(3.0 * top, 0.0), 1.0) if np.isfinite(top) else 0.0
+            cap = int(min(span, mean + 6.0 * mean ** 0.5 + 64.0))
+        cap = int(cap)
+        n_hits = ctypes.c_uint64(0)
+        for _ in range(2):
+            pos, alt, pid = np.zeros(cap, np.uint64), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+            _check(load().kp_spec_simulate(self._h, _ptr(seq), n, ctypes.c_uint32(int(contig_id)), _ptr(rb), _ptr(re),
+                                           ctypes.c_uint64(m), _ptr(r), ctypes.c_double(float(scale)),
+                                           ctypes.c_uint64(int(seed)), ctypes.c_uint32(int(replicate)), ctypes.c_uint64(cap),
+                                           _ptr(pos), _ptr(alt), _ptr(pid), ctypes.byref(n_hits)))
+            if n_hits.value <= cap:
+                break
+            cap = n_hits.value
+        h = n_hits.value
+        return pos[:h].copy(), alt[:h].copy(), pid[:h].copy()
+
+    def spec_sim_stats(self):
+        """Figures of the session's last :meth:`spec_simulate` call (kp_spec_last_sim) as a dict."""
+        st = KPSpecSimStats()
+        _check(load().kp_spec_last_sim(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSpecSimStats._fields_}
 
     def spec_end(self):
         """Close the session (kp_spec_end)."""

@@ -19,6 +19,12 @@ file, rates as Python float reprs.
 the position's (folded) REF base, added in slot order from 0.0 -- the probability that the position
 mutates at all.  A position gets a value only if every one of those types has a pattern for its
 window (and the model has at least one such type): a partly covered position has no value.
+
+``simulate`` draws a random mutation set from the model (``engine.Device.spec_simulate``,
+kp_sim.h) and writes it as ``CHROM POS REF ALT`` lines that ``count``, ``fit`` and ``regions
+--observed`` read: every position mutates into each of its types with the rate of the type's
+pattern, at most once, by a counter-based random number of (seed, contig index, position,
+replicate), so a run is repeatable and a ``--bed`` subset changes no draw.
 """
 import argparse
 import contextlib
@@ -267,6 +273,33 @@ def site_rates(contigs, model, sites, fold=True, host=False):
             if name in sites:
                 out[name] = s.spec_sites(seq, *sites[name])
     return out
+
+
+def simulate(contigs, model, seed, regions=None, scale=1.0, replicate=0, fold=True, host=False, stats=None):
+    """A random mutation set drawn from ``model`` (``engine.Device.spec_simulate``): yields
+    ``(name, pos, alt, pid)`` per contig in genome order -- 0-based positions ascending, the
+    forward-strand ALT bases as upper-case ASCII and the pattern whose rate (times ``scale``)
+    produced each hit.  A position mutates at most once, into each of its types with the
+    probability of the type's pattern.  ``regions``: ``{name: [(begin, end), ...]}``; a contig's
+    regions are merged into their union, a contig without regions draws nothing, None = every
+    whole contig.  The draw depends on ``(seed, contig, position, replicate)`` and the model only,
+    the contig by its 0-based index in genome order: a subset of regions or contigs changes no
+    draw elsewhere, and another ``replicate`` gives an independent set.  A dict ``stats`` gets
+    ``windows`` (valid windows inside the regions), ``hits`` and ``items`` added up."""
+    with session(model, fold, host) as s:
+        for contig_id, (name, seq) in enumerate(contigs):
+            if regions is None:
+                reg = np.array([(0, seq.shape[0])], np.uint64)
+            else:
+                reg = seqio.merge_regions(regions.get(name, np.zeros((0, 2), np.uint64)))
+                if reg.shape[0] and int(reg[-1, 1]) > seq.shape[0]:
+                    raise ValueError(f"a region of {name} ends past the contig's {seq.shape[0]} bases")
+            pos, alt, pid = s.spec_simulate(seq, reg, model.rates, seed, contig_id, replicate, scale)
+            if stats is not None:
+                st = s.spec_sim_stats()
+                for key in ("windows", "hits", "items"):
+                    stats[key] = stats.get(key, 0) + st[key]
+            yield name, pos, alt, pid
 
 
 _CLASS = np.full(256, 4, np.uint8)
@@ -552,6 +585,32 @@ def _run_sites(args, model, fold, host, report, out):
                       for (c, p, r, a), j in zip(rows, pid.tolist())))
 
 
+def _run_simulate(args, model, fold, host, report, out):
+    regions = seqio.read_bed(args.bed) if args.bed else None
+    if not 0 <= args.seed < 1 << 64 or not 0 <= args.replicate < 1 << 32:
+        raise ValueError("--seed must be an unsigned 64-bit and --replicate an unsigned 32-bit integer")
+    seen, seqs = set(), {}
+
+    def contigs():
+        for name, seq in seqio.read_genome(args.genome):
+            seen.add(name)
+            seqs[name] = seq
+            yield name, seq
+
+    stats = {"windows": 0, "hits": 0}
+    per_type = np.zeros(12, np.int64)
+    for name, pos, alt, pid in simulate(contigs(), model, args.seed, regions, args.scale, args.replicate, fold, host, stats):
+        ref = seqs.pop(name)[pos.astype(np.intp)] & 0xDF
+        per_type += np.bincount(model.ptype[pid], minlength=12)
+        out.write("".join(f"{name} {p + 1} {chr(r)} {chr(a)}\n" for p, r, a in zip(pos.tolist(), ref.tolist(), alt.tolist())))
+    report.update(windows=stats["windows"], hits=stats["hits"])
+    kinds = TYPES(False)
+    for t in sorted(set(model.ptype.tolist())):
+        report[f"hits_{kinds[t]}"] = int(per_type[t])
+    if regions is not None:
+        report["unknown_contig_regions"] = sum(len(v) for name, v in regions.items() if name not in seen)
+
+
 def get_parser():
     p = argparse.ArgumentParser(prog="kmerpapa-spectrum",
                                 description="Counts, fits and applies one k-mer pattern partition per mutation type "
@@ -613,6 +672,15 @@ def get_parser():
     sit = sub.add_parser("sites", help="the type, pattern and rate of given mutations")
     applying(sit)
     sit.add_argument("sites", help="File of CHROM POS REF ALT lines, POS 1-based")
+    sim = sub.add_parser("simulate", help="a random mutation set drawn from the model, as CHROM POS REF ALT lines")
+    applying(sim)
+    sim.add_argument("--seed", type=int, required=True,
+                     help="Seed of the draw (0 .. 2^64 - 1): the same seed, replicate, genome and model give the same set")
+    sim.add_argument("--replicate", type=int, default=0, metavar="R",
+                     help="Number of the set (default 0): every replicate of a seed is an independent draw")
+    sim.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every rate by X (default 1)")
+    sim.add_argument("--bed", metavar="FILE", help="Only the positions of these regions (their union); the draws "
+                                                   "inside them are those of a whole-genome run")
     return p
 
 
@@ -653,13 +721,14 @@ def main(argv=None, host=False):
         else:
             model = Model.read(args.model)
             _check_fold(model, fold)
-            run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites}[args.command]
+            run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites, "simulate": _run_simulate}[args.command]
+            streamed = args.command in ("track", "simulate")  # (written contig by contig)
             try:
-                if args.command == "track" and args.output != "-":
-                    with open(args.output, "w") as out:  # (a genome's track is written contig by contig)
+                if streamed and args.output != "-":
+                    with open(args.output, "w") as out:
                         run(args, model, fold, host, report, out)
                 else:
-                    run(args, model, fold, host, report, sys.stdout if args.command == "track" else buf)
+                    run(args, model, fold, host, report, sys.stdout if streamed else buf)
             except KPError as e:
                 if e.code == -1 and "not a partition" in str(e):
                     print(f"kmerpapa-spectrum: a type's patterns are not a partition: {_overlap_report(model)} pairs of "
@@ -677,7 +746,7 @@ def main(argv=None, host=False):
     if args.command in ("count", "fit"):
         return 0
     try:
-        if args.command == "track":
+        if args.command in ("track", "simulate"):
             sys.stdout.flush()
         elif args.output == "-":
             sys.stdout.write(buf.getvalue())

@@ -521,7 +521,41 @@ int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns,
  * draw, one plain store of the item's hits), an exclusive scan of the items' hits whose total is
  * read back (the call ends there if it exceeds cap), and a write kernel that draws again and puts
  * each hit at item offset + thread offset + rank; the order never depends on atomics.  Knob, read at
- * each call (every setting gives the same results): KP_SIM_GRID caps the grid. */
+ * each call (every setting gives the same results): KP_SIM_GRID caps the grid.
+ * Null tables (a call of a spectrum session): many replicates of that draw, counted per region.
+ *   kp_spec_null     Regions are kp_spec_regions' regions: in any order, overlapping or not, empty
+ *                    or not, clipped the same way, nothing merged.  Without by_type the output is
+ *                    counts[n_regions][n_reps]: counts[r][j] = the number of positions p with
+ *                    reg_begin[r] <= p < reg_end[r] at which kp_spec_simulate with the same (seq,
+ *                    contig_id, rates, scale, seed) and replicate = rep_first + j draws a hit -- the
+ *                    window, its validity, the table entry, c0 <= c1 <= c2, u and the slot exactly as
+ *                    described there.  With by_type the output is counts[n_regions][n_reps][12],
+ *                    indexed by the type id ptype[pid] of the pattern that produced the hit; ids
+ *                    6..11 stay 0 under folding, and the 12 entries sum to the entry without
+ *                    by_type.  The result depends on (seed, contig_id, position, replicate) and the
+ *                    model only -- not on the other regions, on how replicates are batched, on the
+ *                    grid, knobs or arrival order: a call with (rep_first = a, n_reps = b) equals
+ *                    columns a .. a + b - 1 of a call with (rep_first = 0, n_reps = a + b).  Counts
+ *                    are integers, so the device result equals the host result bit for bit; a count
+ *                    is at most the region's length, below 2^32 as a contig is, so uint32 cannot wrap.
+ *                    KP_E_STATE outside a session.  KP_E_ARG, checked on the host before any launch
+ *                    and naming the first offender (counts is left untouched): counts or rates NULL;
+ *                    n_reps = 0; rep_first + n_reps > 2^32; a rate or scale kp_spec_simulate
+ *                    rejects; a region with begin > end or past the contig.  KP_E_NOMEM if the table
+ *                    does not fit the arena beside the lookup table (free device memory minus 2 GiB);
+ *                    the lookup table stays where it was, or is built again if the arena grew.
+ *   kp_spec_last_null  figures of the session's last kp_spec_null call.
+ * With ctx = NULL the call runs serially in the host session with the same functions.  The
+ * comparison u < c is made on integers: u = m * 2^-53 with m the 53 bits of the generator's output,
+ * and m < ceil(c * 2^53) holds exactly when u < c does (the product is exact for c in [0, 1]).  On
+ * the device one kernel runs a persistent grid over (work item, replicate chunk) pairs: per batch of
+ * the roll the threads stage every window's three thresholds in LDS, then each wave walks staged
+ * windows with consecutive replicates on its lanes -- the first Philox round does not depend on the
+ * replicate and is done once per window -- and a hit adds to the item's uint32 LDS counter
+ * [replicate][type]; after the item each non-zero counter goes to counts with one global atomic.  A
+ * chunk holds at most 3,072 replicates (256 with by_type); more replicates take several passes over
+ * the item.  Knobs, read at each call (every setting gives the same table): KP_NULL_REPS caps the
+ * replicates per pass, KP_NULL_GRID the grid. */
 typedef struct {
     uint64_t windows; /* valid windows inside the regions                                          */
     uint64_t hits;    /* mutations drawn                                                           */
@@ -529,6 +563,15 @@ typedef struct {
     double count_ms;  /* device time of the count and offsets kernels (HIP events; 0 on the host)  */
     double write_ms;  /* device time of the write kernel (HIP events; 0 on the host or if not run) */
 } kp_spec_sim_stats;
+typedef struct {
+    uint64_t windows;       /* valid windows, summed over the regions                                */
+    uint64_t draws;         /* windows with c2 > 0, times n_reps                                     */
+    uint64_t hits;          /* the sum of the table                                                  */
+    uint64_t items;         /* work items                                                            */
+    uint32_t passes;        /* replicate chunks each item was run in (1 on the host)                 */
+    uint32_t reps_per_pass; /* replicates per chunk, the last one may hold fewer (n_reps on the host) */
+    double null_ms;         /* device time of the kernel (HIP events; 0 on the host)                 */
+} kp_spec_null_stats;
 typedef struct {
     uint64_t assigned;  /* (centre, slot) pairs of the regions calls that fell into a pattern      */
     uint64_t unmatched; /* ... with a valid window and no pattern in the slot                      */
@@ -563,6 +606,10 @@ int kp_spec_simulate(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t conti
                      uint32_t replicate, uint64_t cap, uint64_t *out_pos, uint8_t *out_alt, int32_t *out_pid,
                      uint64_t *n_hits);
 int kp_spec_last_sim(kp_ctx *ctx, kp_spec_sim_stats *out);
+int kp_spec_null(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig_id, const uint64_t *reg_begin,
+                 const uint64_t *reg_end, uint64_t n_regions, const double *rates, double scale, uint64_t seed,
+                 uint32_t rep_first, uint32_t n_reps, int by_type, uint32_t *counts);
+int kp_spec_last_null(kp_ctx *ctx, kp_spec_null_stats *out);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

@@ -44,6 +44,8 @@
 //   kp_sim_*         a random mutation set drawn from a spectrum model (kp_sim.h): the kp_spec roll,
 //                      one counter-based random number per position and an ordered two-pass
 //                      compaction of the hits
+//   kp_null_*        per-region null tables (kp_null.h): the same draw for many replicates at once,
+//                      counted per region and replicate instead of listed
 //
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
@@ -62,6 +64,8 @@
 //                  typed site counting
 //   kp_sim.h       the draw of a mutation set from a spectrum model: Philox per position, the count,
 //                  offsets and write kernels and kp_spec_simulate
+//   kp_null.h      many replicates of that draw binned by region: the roll staged in LDS, the draw
+//                  with the replicates on the lanes, and kp_spec_null
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -85,3 +89,4 @@
 #include "kp_pred.h"
 #include "kp_spec.h"
 #include "kp_sim.h"
+#include "kp_null.h"

@@ -142,6 +142,7 @@ struct kp_spec_sess {
     std::vector<int32_t> h_lut;
     kp_spec_stats st{};
     kp_spec_sim_stats sim{};  // of the last kp_spec_simulate call (kp_sim.h)
+    kp_spec_null_stats null{};  // of the last kp_spec_null call (kp_null.h)
 };
 
 #define KP_SIDE_STREAMS 3

@@ -97,6 +97,12 @@ class KPSpecSimStats(ctypes.Structure):
                 ("count_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
 
 
+class KPSpecNullStats(ctypes.Structure):
+    _fields_ = [("windows", ctypes.c_uint64), ("draws", ctypes.c_uint64), ("hits", ctypes.c_uint64),
+                ("items", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("reps_per_pass", ctypes.c_uint32),
+                ("null_ms", ctypes.c_double)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
@@ -111,7 +117,8 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_seq_end", "kp_seq_last_stats", "kp_seq_host", "kp_pred_begin", "kp_pred_regions", "kp_pred_track",
            "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
            "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
-           "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim"]
+           "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim",
+           "kp_spec_null", "kp_spec_last_null"]
 
 
 def load():
@@ -219,6 +226,10 @@ def load():
             L.kp_spec_simulate.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, ctypes.c_double, u64, u32, u64, vp, vp, vp,
                                            u64p]
             L.kp_spec_last_sim.argtypes = [vp, ctypes.POINTER(KPSpecSimStats)]
+        if hasattr(L, "kp_spec_null"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            L.kp_spec_null.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, ctypes.c_double, u64, u32, u32, ctypes.c_int, vp]
+            L.kp_spec_last_null.argtypes = [vp, ctypes.POINTER(KPSpecNullStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -829,6 +840,34 @@ class _SpecCalls:
         st = KPSpecSimStats()
         _check(load().kp_spec_last_sim(self._h, ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in KPSpecSimStats._fields_}
+
+    def spec_null(self, seq, regions, rates, seed, contig_id=0, rep_first=0, n_reps=1, scale=1.0, by_type=False):
+        """The mutation count of every region in each of ``n_reps`` replicates of
+        :meth:`spec_simulate`'s draw (kp_spec_null): uint32 ``[m, n_reps]``, or with ``by_type``
+        ``[m, n_reps, 12]`` by type id.  Column ``j`` counts the hits of replicate ``rep_first +
+        j``; ``regions`` as :meth:`spec_regions`' (any order, overlapping or not)."""
+        seq, n = _seq_bytes(seq)
+        rb, re, m = _regions_arrays(regions)
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != self._spec_P:
+            raise ValueError("one rate per pattern")
+        for name, v in (("seed", seed), ("contig_id", contig_id), ("rep_first", rep_first), ("n_reps", n_reps)):
+            if not 0 <= int(v) < (1 << 64 if name == "seed" else 1 << 32):
+                raise ValueError(f"{name} must be an unsigned {64 if name == 'seed' else 32}-bit integer")
+        shape = (m, int(n_reps), 12) if by_type else (m, int(n_reps))
+        size = int(np.prod(shape, dtype=np.int64))
+        counts = np.zeros(max(size, 1), np.uint32)  # (never a null pointer)
+        _check(load().kp_spec_null(self._h, _ptr(seq), n, ctypes.c_uint32(int(contig_id)), _ptr(rb), _ptr(re),
+                                   ctypes.c_uint64(m), _ptr(r), ctypes.c_double(float(scale)), ctypes.c_uint64(int(seed)),
+                                   ctypes.c_uint32(int(rep_first)), ctypes.c_uint32(int(n_reps)), int(bool(by_type)),
+                                   _ptr(counts)))
+        return counts[:size].reshape(shape)
+
+    def spec_null_stats(self):
+        """Figures of the session's last :meth:`spec_null` call (kp_spec_last_null) as a dict."""
+        st = KPSpecNullStats()
+        _check(load().kp_spec_last_null(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSpecNullStats._fields_}
 
     def spec_end(self):
         """Close the session (kp_spec_end)."""

@@ -25,6 +25,11 @@ kp_sim.h) and writes it as ``CHROM POS REF ALT`` lines that ``count``, ``fit`` a
 --observed`` read: every position mutates into each of its types with the rate of the type's
 pattern, at most once, by a counter-based random number of (seed, contig index, position,
 replicate), so a run is repeatable and a ``--bed`` subset changes no draw.
+
+``null`` builds the null distribution such draws imply for the mutation count of every region
+(``engine.Device.spec_null``, kp_null.h): ``--replicates`` sets are drawn and counted per region in
+one pass per contig, column ``j`` being exactly ``simulate --replicate F+j``, and each region gets
+the mean, variance and range of its simulated counts and, with ``--observed``, empirical p-values.
 """
 import argparse
 import contextlib
@@ -300,6 +305,79 @@ def simulate(contigs, model, seed, regions=None, scale=1.0, replicate=0, fold=Tr
                 for key in ("windows", "hits", "items"):
                     stats[key] = stats.get(key, 0) + st[key]
             yield name, pos, alt, pid
+
+
+def _contig_null(s, seq, reg, rates, seed, contig_id, first, replicates, scale, by_type, budget, stats=None):
+    """One contig's null table in batches of regions, and of replicates if need be, of at most
+    ``budget`` counters a call."""
+    m, nt = reg.shape[0], 12 if by_type else 1
+    rep_step = max(1, min(int(replicates), int(budget) // nt))
+    reg_step = max(1, int(budget) // (rep_step * nt))
+    out = np.zeros((m, replicates, 12) if by_type else (m, replicates), np.uint32)
+    for b in range(0, m, reg_step):
+        for j in range(0, replicates, rep_step):
+            n = min(rep_step, replicates - j)
+            out[b:b + reg_step, j:j + n] = s.spec_null(seq, reg[b:b + reg_step], rates, seed, contig_id, first + j, n,
+                                                       scale, by_type)
+            if stats is not None:
+                st = s.spec_null_stats()
+                for key in ("windows", "draws", "hits", "items"):
+                    stats[key] = stats.get(key, 0) + st[key]
+    return out
+
+
+def null_table(contigs, model, regions, seed, replicates, first=0, scale=1.0, by_type=False, fold=True, host=False,
+               budget=DEFAULT_BUDGET, stats=None):
+    """The null distribution of the mutation count per region (``engine.Device.spec_null``):
+    ``{contig: table}``, ``table`` uint32 ``[m, replicates]`` (``[m, replicates, 12]`` by type id
+    with ``by_type``).  Column ``j`` holds, per region of ``regions[contig]`` (``(begin, end)``
+    pairs in any order, overlapping or not, nothing merged), the hits :func:`simulate` draws
+    inside it with ``replicate = first + j`` and the same seed, scale and genome: the contig
+    enters the draw by its 0-based index in genome order, exactly as there.  Batching by
+    ``budget`` counters a call changes no result.  A dict ``stats`` gets ``windows``, ``draws``,
+    ``hits`` and ``items`` added up over the calls."""
+    replicates, first = int(replicates), int(first)
+    if replicates < 1 or first < 0 or first + replicates > 1 << 32:
+        raise ValueError("the replicates must be at least one and number below 2^32")
+    out = {}
+    with session(model, fold, host) as s:
+        for contig_id, (name, seq) in enumerate(contigs):
+            if name in regions:
+                out[name] = _contig_null(s, seq, _region_array(regions[name]), model.rates, seed, contig_id, first,
+                                         replicates, scale, by_type, budget, stats)
+    return out
+
+
+def null_summary(total, observed=None):
+    """Per region of a null table ``total [m, R]``: a dict of lists ``mean`` (``S1 / R``), ``var``
+    (the unbiased ``(R * S2 - S1 * S1) / (R * (R - 1))`` from integer sums, one division; nan for
+    ``R == 1``), ``min`` and ``max``; with ``observed [m]`` also the empirical p-values that are
+    never 0 (Phipson & Smyth): ``p_upper = (1 + #{j: sim_j >= obs}) / (R + 1)`` and ``p_lower``
+    with ``<=``."""
+    total = np.asarray(total)
+    if total.ndim != 2 or total.shape[1] < 1:
+        raise ValueError("a null table is [regions, replicates] with at least one replicate")
+    m, R = total.shape
+    out = {"mean": [], "var": [], "min": [], "max": []}
+    if observed is not None:
+        observed = np.asarray(observed).reshape(-1)
+        if observed.shape[0] != m:
+            raise ValueError("one observed count per region")
+        out.update(p_upper=[], p_lower=[])
+    for i in range(m):
+        row = total[i].astype(np.uint64)
+        top = int(row.max())
+        S1 = int(row.sum()) if top * R < 1 << 64 else sum(row.tolist())
+        S2 = int((row * row).sum()) if top * top * R < 1 << 64 else sum(x * x for x in row.tolist())
+        out["mean"].append(S1 / R)
+        out["var"].append((R * S2 - S1 * S1) / (R * (R - 1)) if R > 1 else float("nan"))
+        out["min"].append(int(row.min()))
+        out["max"].append(top)
+        if observed is not None:
+            obs = int(observed[i])
+            out["p_upper"].append((1 + int((total[i] >= obs).sum())) / (R + 1))
+            out["p_lower"].append((1 + int((total[i] <= obs).sum())) / (R + 1))
+    return out
 
 
 _CLASS = np.full(256, 4, np.uint8)
@@ -611,6 +689,91 @@ def _run_simulate(args, model, fold, host, report, out):
         report["unknown_contig_regions"] = sum(len(v) for name, v in regions.items() if name not in seen)
 
 
+def _run_null(args, model, fold, host, report, out):
+    rows = _bed_lines(args.bed)
+    per = _by_contig(rows)
+    n, R, first = len(rows), args.replicates, args.first_replicate
+    if not 0 <= args.seed < 1 << 64:
+        raise ValueError("--seed must be an unsigned 64-bit integer")
+    if R < 1 or first < 0 or first + R > 1 << 32:
+        raise ValueError("--replicates must be at least 1, and --first-replicate + --replicates at most 2^32")
+    tids = sorted(set(model.ptype.tolist()))
+    kinds = [TYPES(False)[t] for t in tids]
+    cols = ["total"] + (kinds if args.by_type else [])  # a summary per column and BED line
+    other = np.zeros((n, 4), np.uint64)
+    exp = np.zeros((n, 12), np.float64)
+    obs = np.zeros((n, 12), np.int64)
+    tables, seen = {}, {}
+    stats = {"windows": 0, "draws": 0, "hits": 0}
+    with session(model, fold, host) as s:
+        for contig_id, (name, seq) in enumerate(seqio.read_genome(args.genome)):
+            if name in per:
+                seen[name] = seq
+                idx = np.array(per[name])
+                reg = np.array([(rows[i][1], rows[i][2]) for i in per[name]], np.uint64)
+                _, o, e = _contig_regions(s, seq, reg, len(model.names), model.rates, False, DEFAULT_BUDGET)
+                other[idx], exp[idx] = o, e
+                tables[name] = _contig_null(s, seq, reg, model.rates, args.seed, contig_id, first, R, args.scale,
+                                            args.by_type, DEFAULT_BUDGET, stats)
+        st = s.spec_stats()
+    report.update(assigned=st["assigned"], unmatched=st["unmatched"], invalid=st["invalid"], windows=stats["windows"],
+                  draws=stats["draws"], hits=stats["hits"],
+                  unknown_contig_regions=sum(len(v) for name, v in per.items() if name not in seen))
+    if args.observed:
+        sites = _observed(args.observed, seen, model, fold, report)
+        for name, by_type in sites.items():
+            idx = np.array(per[name])
+            reg = np.array([(rows[i][1], rows[i][2]) for i in per[name]], np.uint64)
+            for t, pos in by_type.items():
+                obs[idx, t] = np.searchsorted(pos, reg[:, 1], "left") - np.searchsorted(pos, reg[:, 0], "left")
+    obs_total = obs[:, tids].sum(axis=1)
+    summary = [[None] * len(cols) for _ in range(n)]  # per BED line and column: (mean, var, min, max[, p_upper, p_lower])
+    draws = ["0" + " 0" * (R - 1) + "\n"] * n
+    for name, idx in per.items():
+        if name not in tables:
+            tab = np.zeros((len(idx), R, 12) if args.by_type else (len(idx), R), np.uint32)
+        else:
+            tab = tables.pop(name)
+        total = tab.sum(axis=2, dtype=np.uint32) if args.by_type else tab  # (a region's count is below 2^32)
+        for c, col in enumerate(cols):
+            t = None if c == 0 else tids[c - 1]
+            one = total if t is None else tab[:, :, t]
+            ob = None if not args.observed else (obs_total[idx] if t is None else obs[idx, t])
+            sm = null_summary(one, ob)
+            keys = ["mean", "var", "min", "max"] + (["p_upper", "p_lower"] if args.observed else [])
+            for x, i in enumerate(idx):
+                summary[i][c] = [sm[key][x] for key in keys]
+        if args.draws and name in seen:
+            for x, i in enumerate(idx):
+                draws[i] = " ".join(map(str, total[x].tolist())) + "\n"
+    labelled = any(row[3] is not None for row in rows)
+    head = ["#chrom", "start", "end"] + ["name"] * labelled + ["valid", "invalid", "exp_total"]
+    for c, col in enumerate(cols):
+        tail = "" if c == 0 else "_" + col
+        head += [f"sim_mean{tail}", f"sim_var{tail}", f"sim_min{tail}", f"sim_max{tail}"]
+        if args.observed:
+            head += [f"obs_{col}", f"p_upper{tail}", f"p_lower{tail}"]
+    lines = [" ".join(head) + "\n"]
+    for i, (chrom, b, e, label) in enumerate(rows):
+        inv = int(other[i, 3])
+        tok = [chrom, str(b), str(e)] + [label if label is not None else "."] * labelled
+        tok += [str(e - b - inv if chrom in seen else 0), str(inv)]
+        total = 0.0
+        for t in tids:
+            total = total + float(exp[i, t])
+        tok += [repr(total * float(args.scale))]
+        for c in range(len(cols)):
+            v = summary[i][c]
+            tok += [repr(float(v[0])), repr(float(v[1])), str(v[2]), str(v[3])]
+            if args.observed:
+                tok += [str(int(obs_total[i] if c == 0 else obs[i, tids[c - 1]])), repr(float(v[4])), repr(float(v[5]))]
+        lines.append(" ".join(tok) + "\n")
+    out.write("".join(lines))
+    if args.draws:
+        with open(args.draws, "w") as f:
+            f.write("".join(draws))
+
+
 def get_parser():
     p = argparse.ArgumentParser(prog="kmerpapa-spectrum",
                                 description="Counts, fits and applies one k-mer pattern partition per mutation type "
@@ -681,6 +844,20 @@ def get_parser():
     sim.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every rate by X (default 1)")
     sim.add_argument("--bed", metavar="FILE", help="Only the positions of these regions (their union); the draws "
                                                    "inside them are those of a whole-genome run")
+    nul = sub.add_parser("null", help="per region: the null distribution of the mutation count over many simulated "
+                                      "sets, and the empirical p-values of the observed count")
+    applying(nul)
+    nul.add_argument("--bed", metavar="FILE", required=True, help="The regions; a 4th column is carried through as a name")
+    nul.add_argument("--replicates", type=int, required=True, metavar="R", help="Number of simulated sets")
+    nul.add_argument("--seed", type=int, required=True,
+                     help="Seed of the draws (0 .. 2^64 - 1): set j is `simulate --seed SEED --replicate F+j`")
+    nul.add_argument("--first-replicate", type=int, default=0, metavar="F", help="Number of the first set (default 0)")
+    nul.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every rate by X (default 1)")
+    nul.add_argument("--observed", metavar="SITES",
+                     help="CHROM POS REF ALT lines to count per region as `regions --observed` does; adds obs_total "
+                          "and the empirical p_upper = (1 + #{sim >= obs}) / (R + 1) and p_lower (with <=)")
+    nul.add_argument("--by-type", action="store_true", help="The same columns per mutation type of the model as well")
+    nul.add_argument("--draws", metavar="FILE", help="Write the raw totals: one line per region, R integers")
     return p
 
 
@@ -721,7 +898,8 @@ def main(argv=None, host=False):
         else:
             model = Model.read(args.model)
             _check_fold(model, fold)
-            run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites, "simulate": _run_simulate}[args.command]
+            run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites, "simulate": _run_simulate,
+                   "null": _run_null}[args.command]
             streamed = args.command in ("track", "simulate")  # (written contig by contig)
             try:
                 if streamed and args.output != "-":

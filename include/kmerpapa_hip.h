@@ -555,7 +555,58 @@ int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns,
  * [replicate][type]; after the item each non-zero counter goes to counts with one global atomic.  A
  * chunk holds at most 3,072 replicates (256 with by_type); more replicates take several passes over
  * the item.  Knobs, read at each call (every setting gives the same table): KP_NULL_REPS caps the
- * replicates per pass, KP_NULL_GRID the grid. */
+ * replicates per pass, KP_NULL_GRID the grid.
+ * Coding consequences (calls of a spectrum session): expected mutations per transcript by class.
+ *   Transcripts.     A transcript t has a strand tx_strand[t] (0 = +, 1 = -) and the CDS segments
+ *                    tx_first[t] .. tx_first[t + 1] - 1 of seg_begin / seg_end on the call's contig:
+ *                    0-based half-open, non-empty, ascending and non-overlapping (abutting segments
+ *                    have no intron between them); tx_first[0] = 0, tx_first[n_tx] = n_segs.  The
+ *                    lengths of a transcript's segments sum to a multiple of 3.  Transcripts may
+ *                    overlap each other in any way; each is computed on its own.  KP_E_ARG, checked on
+ *                    the host before any launch and naming the first offending transcript, for
+ *                    anything else; also splice > 8.
+ *   Codons.          The spliced index of position g of segment e is j = (the lengths of the
+ *                    transcript's segments before e) + g - seg_begin[e], in genomic orientation on
+ *                    both strands.  The codon of g is the spliced bytes x0 x1 x2 at 3 (j / 3) .. + 2
+ *                    -- it may span two or three segments -- read on the - strand as (comp x2, comp
+ *                    x1, comp x0).  Lower case counts as upper case.
+ *   Classes.         Every coding position has three (position, forward ALT) pairs, the bases other
+ *                    than its own.  A pair's class comes from the standard genetic code applied to
+ *                    the transcript-strand codon before and after the change: 0 synonymous (the same
+ *                    amino acid, or stop to stop), 1 missense, 2 nonsense (amino acid to stop), 3
+ *                    stop-lost (stop to amino acid); 4 = every pair of an essential splice position:
+ *                    an intronic base within `splice` bases of either end of an intron between two
+ *                    consecutive segments -- for the intron [a, b) the positions [a, min(a + splice,
+ *                    b)) and [max(b - splice, a), b), each once.  A coding position whose codon holds
+ *                    a byte that is none of ACGTacgt, and a splice position whose own byte is none,
+ *                    has no class and counts once in other[7].
+ *   Rates.           The pattern of a pair is kp_spec_sites' (the window's code, the slot of the
+ *                    folded ALT).  The class never depends on the window: a pair whose window is
+ *                    invalid or leaves the contig still has a class and is counted, without a pattern.
+ *   kp_spec_coding   hist[n_tx][5][n_patterns] (may be NULL): the pairs of class c whose pattern is
+ *                    p.  other[n_tx][8]: [0..4] all pairs per class, rated or not (the mutational
+ *                    opportunity); [5] pairs with an invalid window; [6] pairs with a valid window
+ *                    and no pattern in their slot; [7] positions without a class.  So sum(other[0..4])
+ *                    = sum(hist) + other[5] + other[6], and 3 x positions = sum(other[0..4]) + 3 x
+ *                    other[7].  With rates (may be NULL) expected[n_tx][5][12]: kp_spec_regions' sum
+ *                    of row [t][c] of hist per type id.  Other argument and state errors, and the
+ *                    arena, as kp_spec_regions'.
+ *   kp_spec_coding_sites  One result per (site, transcript) pair i: position pos[i] with the forward
+ *                    ALT alt[i] (checked as kp_spec_sites checks them) in transcript tx[i] < n_tx.
+ *                    cls[i] = the class 0..4, or -1: the position is neither coding nor an essential
+ *                    splice position of that transcript; -2: it has no class; -3: ALT equals REF (in
+ *                    this order of precedence).  pid[i] as kp_spec_sites' output.  codons[i] = the
+ *                    transcript-strand REF codon (16 b0 + 4 b1 + b2, ACGT digits) | ALT codon << 6
+ *                    for classes 0..3, else 0.
+ *   kp_spec_last_coding  figures of the session's last kp_spec_coding call.
+ * With ctx = NULL the calls run serially in the host session with the same per-pair functions.  On
+ * the device kp_spec_coding runs kp_spec_regions' persistent grid and roll over pieces of one segment
+ * or of one splice interval; a record per segment carries the transcript, the strand, the spliced
+ * index of its first base and the two spliced bases before and after it, so nothing outside the
+ * segment is read for a codon.  Counters [5][n_patterns] are uint32 in LDS per item while n_patterns
+ * <= 3,276 (5 x 4 x n_patterns <= 64 KiB), global 64-bit atomics otherwise.  Knobs, read at each call
+ * (every setting gives the same results): KP_CODING_GLOBAL, KP_CODING_LDS_P and KP_CODING_GRID, with
+ * the meaning of their KP_SPEC_* counterparts. */
 typedef struct {
     uint64_t windows; /* valid windows inside the regions                                          */
     uint64_t hits;    /* mutations drawn                                                           */
@@ -584,6 +635,13 @@ typedef struct {
     uint32_t path;      /* of the last regions call: 0 none or host, 1 LDS counters, 2 global
                            atomics                                                                 */
 } kp_spec_stats;
+typedef struct {
+    uint64_t items;     /* work items                                                              */
+    uint64_t positions; /* coding and essential splice positions, summed over the transcripts      */
+    uint64_t pairs;     /* (position, ALT) pairs with a class: the sum of other[0..4]              */
+    double scan_ms;     /* device time of the scan kernel (HIP events; 0 on the host)              */
+    uint32_t path;      /* 0 none or host, 1 LDS counters, 2 global atomics                        */
+} kp_spec_coding_stats;
 int kp_seq_begin_typed(kp_ctx *ctx, int k, int fold);
 int kp_seq_sites_typed(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt,
                        uint64_t n_sites);
@@ -610,6 +668,14 @@ int kp_spec_null(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig_id
                  const uint64_t *reg_end, uint64_t n_regions, const double *rates, double scale, uint64_t seed,
                  uint32_t rep_first, uint32_t n_reps, int by_type, uint32_t *counts);
 int kp_spec_last_null(kp_ctx *ctx, kp_spec_null_stats *out);
+int kp_spec_coding(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *seg_begin, const uint64_t *seg_end,
+                   uint64_t n_segs, const uint64_t *tx_first, const uint8_t *tx_strand, uint64_t n_tx, uint32_t splice,
+                   const double *rates, uint64_t *hist, uint64_t *other, double *expected);
+int kp_spec_coding_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *seg_begin, const uint64_t *seg_end,
+                         uint64_t n_segs, const uint64_t *tx_first, const uint8_t *tx_strand, uint64_t n_tx,
+                         uint32_t splice, const uint64_t *pos, const uint8_t *alt, const uint32_t *tx, uint64_t n_pairs,
+                         int32_t *cls, int32_t *pid, uint32_t *codons);
+int kp_spec_last_coding(kp_ctx *ctx, kp_spec_coding_stats *out);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

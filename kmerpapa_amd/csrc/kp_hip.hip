@@ -47,6 +47,10 @@
 //   kp_null_*        per-region null tables (kp_null.h): the same draw for many replicates at once,
 //                      counted per region and replicate instead of listed
 //
+//   kp_coding_*      expected mutations per transcript by coding consequence (kp_coding.h): the
+//                      kp_spec roll over CDS segments and splice intervals, a centre's codon from
+//                      its neighbours and a per-segment record, counters per (class, pattern)
+//
 // One translation unit; the code lives in headers by subsystem:
 //   kp_rt.h        host runtime: errors, allocation helpers, knobs, kp_ctx, kp_create
 //   kp_core.h / kp_libm.h / kp_plan.h   arithmetic, logs and the host plan (shared with tests/emu)
@@ -66,6 +70,8 @@
 //                  offsets and write kernels and kp_spec_simulate
 //   kp_null.h      many replicates of that draw binned by region: the roll staged in LDS, the draw
 //                  with the replicates on the lanes, and kp_spec_null
+//   kp_coding.h    the genetic code and per-pair class functions, the coding scan and sites kernels,
+//                  kp_spec_coding and kp_spec_coding_sites
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -90,3 +96,4 @@
 #include "kp_spec.h"
 #include "kp_sim.h"
 #include "kp_null.h"
+#include "kp_coding.h"

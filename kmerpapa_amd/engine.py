@@ -103,6 +103,11 @@ class KPSpecNullStats(ctypes.Structure):
                 ("null_ms", ctypes.c_double)]
 
 
+class KPSpecCodingStats(ctypes.Structure):
+    _fields_ = [("items", ctypes.c_uint64), ("positions", ctypes.c_uint64), ("pairs", ctypes.c_uint64),
+                ("scan_ms", ctypes.c_double), ("path", ctypes.c_uint32)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
@@ -118,7 +123,7 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
            "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
            "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim",
-           "kp_spec_null", "kp_spec_last_null"]
+           "kp_spec_null", "kp_spec_last_null", "kp_spec_coding", "kp_spec_coding_sites", "kp_spec_last_coding"]
 
 
 def load():
@@ -230,6 +235,12 @@ def load():
             u64, u32 = ctypes.c_uint64, ctypes.c_uint32
             L.kp_spec_null.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, ctypes.c_double, u64, u32, u32, ctypes.c_int, vp]
             L.kp_spec_last_null.argtypes = [vp, ctypes.POINTER(KPSpecNullStats)]
+        if hasattr(L, "kp_spec_coding"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            table = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u32]  # ctx, the contig and the transcript table, splice
+            L.kp_spec_coding.argtypes = table + [vp, vp, vp, vp]
+            L.kp_spec_coding_sites.argtypes = table + [vp, vp, vp, u64, vp, vp, vp]
+            L.kp_spec_last_coding.argtypes = [vp, ctypes.POINTER(KPSpecCodingStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -740,6 +751,24 @@ def pred_host(k, patterns, super_word, fold, seq, regions=None, rates=None, trac
             {name: getattr(st, name) for name, _ in KPPredStats._fields_})
 
 
+def _transcript_arrays(transcripts):
+    """``(seg_begin, seg_end, tx_first, tx_strand)`` of ``(strand, segments)`` pairs."""
+    sb, se, first, strand = [], [], [0], []
+    for st, segs in transcripts:
+        st = {"+": 0, "-": 1}.get(st, st)
+        if st not in (0, 1):
+            raise ValueError("a strand is 0 / '+' or 1 / '-'")
+        strand.append(st)
+        for b, e in segs:
+            sb.append(int(b))
+            se.append(int(e))
+        first.append(len(sb))
+    if any(x < 0 for x in sb) or any(x < 0 for x in se):
+        raise ValueError("a negative segment coordinate")
+    return (np.array(sb, np.uint64), np.array(se, np.uint64), np.array(first, np.uint64),
+            np.array(strand, np.uint8))
+
+
 class _SpecCalls:
     """The kp_spec_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
     calling thread's host session (:class:`HostSpec`)."""
@@ -868,6 +897,61 @@ class _SpecCalls:
         st = KPSpecNullStats()
         _check(load().kp_spec_last_null(self._h, ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in KPSpecNullStats._fields_}
+
+    def spec_coding(self, seq, transcripts, splice=2, rates=None, want_hist=True):
+        """Per transcript of the contig ``seq`` the (position, ALT) pairs by coding consequence
+        (kp_spec_coding): ``(hist, other, expected)`` -- ``hist`` uint64 ``[m, 5, P]`` per class
+        (synonymous, missense, nonsense, stop-lost, essential splice) and pattern (None without
+        ``want_hist``), ``other`` uint64 ``[m, 8]`` = all pairs per class, pairs with an invalid
+        window, pairs without a pattern, positions without a class, ``expected`` float64 ``[m, 5,
+        12]`` per class and type id (None without ``rates``).  ``transcripts``: ``(strand, segments)``
+        each, ``strand`` 0 or 1 (or ``+`` / ``-``), ``segments`` ascending 0-based half-open
+        ``(begin, end)`` pairs whose lengths sum to a multiple of 3."""
+        seq, n = _seq_bytes(seq)
+        sb, se, first, strand = _transcript_arrays(transcripts)
+        m, P = strand.shape[0], self._spec_P
+        r = exp = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+            if r.shape[0] != P:
+                raise ValueError("one rate per pattern")
+            exp = np.zeros((m, 5, 12), np.float64)
+        hist = np.zeros((m, 5, P), np.uint64) if want_hist else None
+        other = np.zeros((m, 8), np.uint64)
+        _check(load().kp_spec_coding(self._h, _ptr(seq), n, _ptr(sb), _ptr(se), ctypes.c_uint64(sb.shape[0]), _ptr(first),
+                                     _ptr(strand), ctypes.c_uint64(m), ctypes.c_uint32(int(splice)), _ptr(r), _ptr(hist),
+                                     _ptr(other), _ptr(exp)))
+        return hist, other, exp
+
+    def spec_coding_sites(self, seq, transcripts, pos, alt, tx, splice=2):
+        """One result per (site, transcript) pair (kp_spec_coding_sites): ``(cls, pid, codons)`` --
+        ``cls`` int32 the class 0..4, -1 where the position is neither coding nor an essential
+        splice position of transcript ``tx[i]``, -2 without a class, -3 where ALT equals REF;
+        ``pid`` as :meth:`spec_sites`; ``codons`` uint32 = the transcript-strand REF codon | ALT
+        codon << 6 (6 bits each, ``16 b0 + 4 b1 + b2``) for classes 0..3."""
+        seq, n = _seq_bytes(seq)
+        sb, se, first, strand = _transcript_arrays(transcripts)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        alt = _alt_bytes(alt, pos.shape[0])
+        tx = np.asarray(tx, dtype=np.int64).reshape(-1)
+        if tx.shape[0] != pos.shape[0]:
+            raise ValueError("one transcript per site")
+        if np.any(tx < 0) or np.any(tx >= 1 << 32):
+            raise ValueError("a transcript index that is no uint32")
+        tx = np.ascontiguousarray(tx, dtype=np.uint32)
+        m = pos.shape[0]
+        cls, pid, codons = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint32)
+        _check(load().kp_spec_coding_sites(self._h, _ptr(seq), n, _ptr(sb), _ptr(se), ctypes.c_uint64(sb.shape[0]),
+                                           _ptr(first), _ptr(strand), ctypes.c_uint64(strand.shape[0]),
+                                           ctypes.c_uint32(int(splice)), _ptr(pos), _ptr(alt), _ptr(tx), ctypes.c_uint64(m),
+                                           _ptr(cls), _ptr(pid), _ptr(codons)))
+        return cls, pid, codons
+
+    def spec_coding_stats(self):
+        """Figures of the session's last :meth:`spec_coding` call (kp_spec_last_coding) as a dict."""
+        st = KPSpecCodingStats()
+        _check(load().kp_spec_last_coding(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSpecCodingStats._fields_}
 
     def spec_end(self):
         """Close the session (kp_spec_end)."""

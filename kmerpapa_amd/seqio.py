@@ -1,5 +1,6 @@
 """Readers for the inputs of :mod:`kmerpapa_amd.count` (host code, numpy): genomes as FASTA or
-UCSC ``.2bit``, regions as BED, mutation sites as ``CHROM POS REF ALT`` lines.
+UCSC ``.2bit``, regions as BED, mutation sites as ``CHROM POS REF ALT`` lines, and for
+:mod:`kmerpapa_amd.spectrum` the CDS of transcripts as GTF or BED6.
 
 A contig is ``(name, uint8 array)``, one byte per base, exactly as the file spells it: lower-case
 soft-masking is kept, since the counting kernel reads either case, and every byte other than
@@ -132,6 +133,96 @@ def read_bed(path_or_file):
         except ValueError:
             raise ValueError(f"bad BED line:\n{line.strip()}") from None
     return {name: merge_regions(v) for name, v in per.items()}
+
+
+class Transcript:
+    """The CDS of one transcript: ``name``, ``gene`` (or None), ``contig``, ``strand`` (0 = ``+``,
+    1 = ``-``) and ``segments``, ascending 0-based half-open ``(begin, end)`` pairs."""
+
+    def __init__(self, name, gene, contig, strand, segments):
+        self.name, self.gene, self.contig, self.strand = name, gene, contig, strand
+        self.segments = segments
+
+    @property
+    def length(self):
+        return sum(e - b for b, e in self.segments)
+
+
+def _transcripts(rows, what):
+    """``rows``: ``(name, gene, contig, strand text, begin, end)`` in file order.  Transcripts in
+    the order of their first line, segments sorted.  A transcript on two contigs or strands, or
+    with overlapping segments, is a ValueError."""
+    out = {}
+    for name, gene, contig, strand, b, e in rows:
+        if strand not in ("+", "-"):
+            raise ValueError(f"{what}: transcript {name} has strand {strand!r}, not + or -")
+        if b < 0 or b >= e:
+            raise ValueError(f"{what}: transcript {name} has an empty or reversed segment {b} {e}")
+        t = out.setdefault(name, Transcript(name, gene, contig, "+-".index(strand), []))
+        if t.contig != contig:
+            raise ValueError(f"{what}: transcript {name} lies on two contigs, {t.contig} and {contig}")
+        if t.strand != "+-".index(strand):
+            raise ValueError(f"{what}: transcript {name} lies on both strands")
+        if t.gene is None:
+            t.gene = gene
+        t.segments.append((b, e))
+    for t in out.values():
+        t.segments.sort()
+        for (_, e0), (b1, _) in zip(t.segments[:-1], t.segments[1:]):
+            if b1 < e0:
+                raise ValueError(f"{what}: transcript {t.name} has overlapping segments")
+    return list(out.values())
+
+
+def _gtf_attributes(text):
+    out = {}
+    for field in text.split(";"):
+        tok = field.strip().split(None, 1)
+        if len(tok) == 2:
+            out.setdefault(tok[0], tok[1].strip().strip('"'))
+    return out
+
+
+def read_gtf_cds(path_or_file):
+    """The ``CDS`` lines of a GTF file as :class:`Transcript` objects grouped by
+    ``transcript_id``, in the order of their first line; ``gene`` is the ``gene_name`` attribute,
+    or ``gene_id`` without one.  Coordinates are 1-based inclusive; the frame column is ignored;
+    ``#`` lines and other features are skipped.  (GFF3 is not read.)"""
+    rows = []
+    for line in _read_all(path_or_file).decode("ascii", errors="replace").splitlines():
+        if not line.strip() or line.startswith("#"):
+            continue
+        tok = line.rstrip("\r\n").split("\t")
+        if len(tok) < 9:
+            raise ValueError(f"bad GTF line (nine tab-separated columns):\n{line.strip()}")
+        if tok[2] != "CDS":
+            continue
+        attr = _gtf_attributes(tok[8])
+        if "transcript_id" not in attr:
+            raise ValueError(f"a CDS line without a transcript_id:\n{line.strip()}")
+        try:
+            b, e = int(tok[3]) - 1, int(tok[4])
+        except ValueError:
+            raise ValueError(f"bad GTF line:\n{line.strip()}") from None
+        rows.append((attr["transcript_id"], attr.get("gene_name", attr.get("gene_id")), tok[0], tok[6], b, e))
+    return _transcripts(rows, "GTF")
+
+
+def read_cds_bed(path_or_file):
+    """BED6 lines, one per CDS segment: column 4 the transcript's name, column 6 its strand
+    (0-based half-open coordinates; ``#``, ``track`` and ``browser`` lines skipped)."""
+    rows = []
+    for line in _read_all(path_or_file).decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if not tok or tok[0].startswith("#") or tok[0] in ("track", "browser"):
+            continue
+        if len(tok) < 6:
+            raise ValueError(f"bad BED6 line (chrom start end name score strand):\n{line.strip()}")
+        try:
+            rows.append((tok[3], None, tok[0], tok[5], int(tok[1]), int(tok[2])))
+        except ValueError:
+            raise ValueError(f"bad BED6 line:\n{line.strip()}") from None
+    return _transcripts(rows, "BED")
 
 
 def fold_type(ref, alt):

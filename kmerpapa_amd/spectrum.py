@@ -30,6 +30,14 @@ replicate), so a run is repeatable and a ``--bed`` subset changes no draw.
 (``engine.Device.spec_null``, kp_null.h): ``--replicates`` sets are drawn and counted per region in
 one pass per contig, column ``j`` being exactly ``simulate --replicate F+j``, and each region gets
 the mean, variance and range of its simulated counts and, with ``--observed``, empirical p-values.
+
+``coding`` gives the table a burden or constraint test reads: per transcript the expected number of
+synonymous, missense, nonsense, stop-lost and essential-splice mutations beside the mutational
+opportunity and, with ``--observed``, the observed ones (``engine.Device.spec_coding``,
+kp_coding.h).  The class of a (position, ALT) pair comes from the standard genetic code and the
+transcript's CDS (``--gtf`` or ``--cds-bed``); its rate is the model's, as ``sites`` reports it.
+``consequences`` writes the class, codons and amino acids of given mutations, one line per site
+and transcript.
 """
 import argparse
 import contextlib
@@ -378,6 +386,104 @@ def null_summary(total, observed=None):
             out["p_upper"].append((1 + int((total[i] >= obs).sum())) / (R + 1))
             out["p_lower"].append((1 + int((total[i] <= obs).sum())) / (R + 1))
     return out
+
+
+CLASSES = ["synonymous", "missense", "nonsense", "stop_lost", "splice"]
+# the amino acid of codon 16 b0 + 4 b1 + b2 (ACGT digits), the standard genetic code
+AMINO = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
+
+
+def codon_text(index):
+    return BASES[index >> 4 & 3] + BASES[index >> 2 & 3] + BASES[index & 3]
+
+
+def _usable(transcripts, lengths):
+    """Per transcript: 0 usable, 1 its CDS length is no multiple of 3, 2 its contig is unknown."""
+    return np.array([1 if t.length % 3 else (0 if t.contig in lengths else 2) for t in transcripts], np.int64)
+
+
+def _contig_coding(s, seq, txs, splice, P, rates, budget):
+    """One contig's transcripts in batches of at most ``budget`` counters a call."""
+    m = len(txs)
+    step = max(1, int(budget) // max(5 * P, 1))
+    other = np.zeros((m, 8), np.uint64)
+    exp = np.zeros((m, 5, 12), np.float64)
+    for b in range(0, m, step):
+        _, o, e = s.spec_coding(seq, [(t.strand, t.segments) for t in txs[b:b + step]], splice, rates, want_hist=False)
+        other[b:b + step], exp[b:b + step] = o, e
+    return other, exp
+
+
+def coding_rates(contigs, model, transcripts, splice=2, scale=1.0, by_type=False, fold=True, host=False,
+                 budget=DEFAULT_BUDGET):
+    """Expected mutations per transcript by coding consequence (``engine.Device.spec_coding``).
+    ``transcripts``: ``seqio.Transcript`` objects (``seqio.read_gtf_cds`` / ``read_cds_bed``).
+    Returns a dict of arrays with one row per transcript, in their order: ``other`` uint64 ``[T,
+    8]`` (the pairs of class synonymous, missense, nonsense, stop-lost and essential splice --
+    the mutational opportunity --, the pairs with an invalid window, those without a pattern, the
+    positions without a class), ``expected`` float64 ``[T, 5]`` = per class the sum of its twelve
+    type sums in ascending type order, times ``scale``; with ``by_type`` also ``expected_by_type``
+    ``[T, 5, 12]``, each type sum times ``scale``; ``status`` int64 ``[T]``: 0 computed, 1 skipped
+    because the CDS length is no multiple of 3, 2 on a contig the genome does not have (their rows
+    are zero).  Batching by ``budget`` counters a call changes no result."""
+    transcripts = list(transcripts)
+    T = len(transcripts)
+    other = np.zeros((T, 8), np.uint64)
+    exp = np.zeros((T, 5, 12), np.float64)
+    per = {}
+    for i, t in enumerate(transcripts):
+        if t.length % 3 == 0:
+            per.setdefault(t.contig, []).append(i)
+    seen = set()
+    with session(model, fold, host) as s:
+        for name, seq in contigs:
+            seen.add(name)
+            if name in per:
+                idx = np.array(per[name])
+                o, e = _contig_coding(s, seq, [transcripts[i] for i in per[name]], splice, len(model.names), model.rates,
+                                      budget)
+                other[idx], exp[idx] = o, e
+    total = np.zeros((T, 5), np.float64)
+    for t in range(12):
+        total = total + exp[:, :, t]
+    out = {"other": other, "expected": total * float(scale), "status": _usable(transcripts, seen)}
+    if by_type:
+        out["expected_by_type"] = exp * float(scale)
+    return out
+
+
+def site_pairs(txs, pos):
+    """The (site, transcript) pairs of one contig whose site lies inside the transcript's span
+    (first CDS base to last), by interval search over the sorted positions: ``(site index,
+    transcript index)`` arrays ordered by site, then transcript."""
+    pos = np.asarray(pos, np.uint64)
+    order = np.argsort(pos, kind="stable")
+    ranked = pos[order]
+    si, ti = [], []
+    for j, t in enumerate(txs):
+        if not t.segments:
+            continue
+        lo = np.searchsorted(ranked, np.uint64(t.segments[0][0]), "left")
+        hi = np.searchsorted(ranked, np.uint64(t.segments[-1][1]), "left")
+        si.append(order[lo:hi])
+        ti.append(np.full(hi - lo, j, np.int64))
+    si = np.concatenate(si) if si else np.zeros(0, np.int64)
+    ti = np.concatenate(ti) if ti else np.zeros(0, np.int64)
+    keep = np.lexsort((ti, si))
+    return si[keep].astype(np.int64), ti[keep]
+
+
+def coding_sites(s, seq, txs, pos, alt, splice=2):
+    """The consequences of one contig's sites in its transcripts ``txs``, in the open session
+    ``s``: ``(site index, transcript index, cls, pid, codons)`` of every pair whose site is a
+    coding or essential splice position of the transcript (``engine.Device.spec_coding_sites``)."""
+    si, ti = site_pairs(txs, pos)
+    if not si.shape[0]:
+        return si, ti, np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32)
+    cls, pid, codons = s.spec_coding_sites(seq, [(t.strand, t.segments) for t in txs], np.asarray(pos, np.uint64)[si],
+                                           np.asarray(alt, np.uint8)[si], ti, splice)
+    keep = cls != -1
+    return si[keep], ti[keep], cls[keep], pid[keep], codons[keep]
 
 
 _CLASS = np.full(256, 4, np.uint8)
@@ -774,6 +880,117 @@ def _run_null(args, model, fold, host, report, out):
             f.write("".join(draws))
 
 
+def _read_transcripts(args):
+    return seqio.read_gtf_cds(args.gtf) if args.gtf else seqio.read_cds_bed(args.cds_bed)
+
+
+def _check_splice(splice):
+    if not 0 <= splice <= 8:
+        raise ValueError("--splice must be 0..8")
+
+
+def _run_coding(args, model, fold, host, report, out):
+    _check_splice(args.splice)
+    txs = _read_transcripts(args)
+    T = len(txs)
+    seqs = {}
+
+    def contigs():
+        for name, seq in seqio.read_genome(args.genome):
+            if args.observed:
+                seqs[name] = seq
+            yield name, seq
+
+    res = coding_rates(contigs(), model, txs, args.splice, args.scale, args.by_type, fold, host)
+    status, other, exp = res["status"], res["other"], res["expected"]
+    report.update(transcripts=T, skipped_length=int((status == 1).sum()), unknown_contig_transcripts=int((status == 2).sum()))
+    obs = np.zeros((T, 5), np.int64)
+    if args.observed:
+        raw = _matched_sites(args.observed, report)
+        per = {}
+        for i, t in enumerate(txs):
+            if status[i] == 0:
+                per.setdefault(t.contig, []).append(i)
+        outside = 0
+        with session(model, fold, host) as s:
+            for name, seq in seqs.items():
+                if name not in raw:
+                    continue
+                pos, ref, alt = _keep_matching(seq, *raw[name], report)
+                own = [txs[i] for i in per.get(name, [])]
+                si, ti, cls, _, _ = coding_sites(s, seq, own, pos, alt, args.splice)
+                hit = cls >= 0
+                np.add.at(obs, (np.array(per.get(name, []), np.int64)[ti[hit]], cls[hit]), 1)
+                outside += pos.shape[0] - np.unique(si).shape[0]
+        report["unknown_contig"] = sum(len(v[0]) for name, v in raw.items() if name not in seqs)
+        report["observed_outside"] = outside
+    tids = sorted(set(model.ptype.tolist()))
+    kinds = [TYPES(False)[t] for t in tids]
+    head = ["#name", "gene", "contig", "strand", "cds_bases"] + [f"opp_{c}" for c in CLASSES] + [f"exp_{c}" for c in CLASSES]
+    head += ["unrated", "no_class"]
+    if args.observed:
+        head += [f"obs_{c}" for c in CLASSES]
+    if args.by_type:
+        head += [f"exp_{c}_{x}" for c in CLASSES for x in kinds]
+    lines = [" ".join(head) + "\n"]
+    for i, t in enumerate(txs):
+        tok = [t.name, t.gene if t.gene is not None else ".", t.contig, "+-"[t.strand], str(t.length)]
+        tok += [str(int(x)) for x in other[i, :5]] + [repr(float(x)) for x in exp[i]]
+        tok += [str(int(other[i, 5] + other[i, 6])), str(int(other[i, 7]))]
+        if args.observed:
+            tok += [str(int(x)) for x in obs[i]]
+        if args.by_type:
+            tok += [repr(float(res["expected_by_type"][i, c, ty])) for c in range(5) for ty in tids]
+        lines.append(" ".join(tok) + "\n")
+    out.write("".join(lines))
+
+
+def _run_consequences(args, model, fold, host, report, out):
+    _check_splice(args.splice)
+    txs = _read_transcripts(args)
+    rows, skipped = _site_lines(args.sites)
+    per_rows = _by_contig(rows)
+    report.update(transcripts=len(txs), skipped_length=sum(1 for t in txs if t.length % 3), lines=len(rows) + skipped,
+                  not_snv=skipped, off_contig=0, ref_mismatch=0)
+    per = {}
+    for t in txs:
+        if t.length % 3 == 0:
+            per.setdefault(t.contig, []).append(t)
+    seen = set()
+    kinds = TYPES(False)
+    rates = model.rates.tolist()
+    found = [[] for _ in rows]  # per site: its lines, transcripts in input order
+    with session(model, fold, host) as s:
+        for name, seq in seqio.read_genome(args.genome):
+            seen.add(name)
+            if name not in per_rows:
+                continue
+            idx = np.array(per_rows[name])
+            pos = np.array([rows[i][1] - 1 for i in per_rows[name]], np.uint64)
+            ref = np.array([ord(rows[i][2].upper()) for i in per_rows[name]], np.uint8)
+            alt = np.array([ord(rows[i][3].upper()) for i in per_rows[name]], np.uint8)
+            on = pos < np.uint64(seq.shape[0])
+            same = np.zeros(pos.shape[0], bool)
+            same[on] = (seq[pos[on].astype(np.intp)] & 0xDF) == ref[on]
+            report["off_contig"] += int((~on).sum())
+            report["ref_mismatch"] += int((on & ~same).sum())
+            idx, pos, alt = idx[same], pos[same], alt[same]
+            own = per.get(name, [])
+            for i, j, c, p, cod in zip(*[x.tolist() for x in coding_sites(s, seq, own, pos, alt, args.splice)]):
+                model_part = f"{kinds[int(model.ptype[p])]} {model.names[p]} {rates[p]!r}" if p >= 0 else "NA NA NA"
+                if 0 <= c <= 3:
+                    rc, ac = cod & 63, cod >> 6 & 63
+                    tail = f"{CLASSES[c]} {codon_text(rc)} {codon_text(ac)} {AMINO[rc]} {AMINO[ac]}"
+                else:
+                    tail = (CLASSES[4] if c == 4 else "NA") + " NA NA NA NA"
+                chrom, p1, r, a = rows[int(idx[i])]
+                found[int(idx[i])].append(f"{chrom} {p1} {r} {a} {model_part} {own[j].name} {tail}\n")
+    report["unknown_contig"] = sum(len(v) for name, v in per_rows.items() if name not in seen)
+    report["unknown_contig_transcripts"] = sum(1 for t in txs if t.contig not in seen)
+    report["sites_outside"] = sum(1 for x in found if not x)
+    out.write("".join(line for lines in found for line in lines))
+
+
 def get_parser():
     p = argparse.ArgumentParser(prog="kmerpapa-spectrum",
                                 description="Counts, fits and applies one k-mer pattern partition per mutation type "
@@ -858,6 +1075,25 @@ def get_parser():
                           "and the empirical p_upper = (1 + #{sim >= obs}) / (R + 1) and p_lower (with <=)")
     nul.add_argument("--by-type", action="store_true", help="The same columns per mutation type of the model as well")
     nul.add_argument("--draws", metavar="FILE", help="Write the raw totals: one line per region, R integers")
+
+    def annotated(q):
+        src = q.add_mutually_exclusive_group(required=True)
+        src.add_argument("--gtf", metavar="FILE", help="The transcripts: the CDS lines of a GTF file, grouped by transcript_id")
+        src.add_argument("--cds-bed", metavar="FILE",
+                         help="The transcripts: BED6 lines, one per CDS segment, column 4 the transcript, column 6 the strand")
+        q.add_argument("--splice", type=int, default=2, metavar="N",
+                       help="Intronic bases at each end of an intron that are essential splice positions (0..8, default 2)")
+
+    cod = sub.add_parser("coding", help="per transcript: expected, possible and observed mutations by coding consequence")
+    applying(cod)
+    annotated(cod)
+    cod.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every expected count by X (default 1)")
+    cod.add_argument("--observed", metavar="SITES", help="CHROM POS REF ALT lines to count per transcript and class")
+    cod.add_argument("--by-type", action="store_true", help="The expected counts per class and mutation type of the model as well")
+    con = sub.add_parser("consequences", help="the class, codons and amino acids of given mutations, per transcript")
+    applying(con)
+    annotated(con)
+    con.add_argument("sites", help="File of CHROM POS REF ALT lines, POS 1-based")
     return p
 
 
@@ -899,7 +1135,7 @@ def main(argv=None, host=False):
             model = Model.read(args.model)
             _check_fold(model, fold)
             run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites, "simulate": _run_simulate,
-                   "null": _run_null}[args.command]
+                   "null": _run_null, "coding": _run_coding, "consequences": _run_consequences}[args.command]
             streamed = args.command in ("track", "simulate")  # (written contig by contig)
             try:
                 if streamed and args.output != "-":

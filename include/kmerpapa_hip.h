@@ -606,7 +606,47 @@ int kp_pred_host(int k, int fold, const uint64_t *patterns, uint32_t n_patterns,
  * segment is read for a codon.  Counters [5][n_patterns] are uint32 in LDS per item while n_patterns
  * <= 3,276 (5 x 4 x n_patterns <= 64 KiB), global 64-bit atomics otherwise.  Knobs, read at each call
  * (every setting gives the same results): KP_CODING_GLOBAL, KP_CODING_LDS_P and KP_CODING_GRID, with
- * the meaning of their KP_SPEC_* counterparts. */
+ * the meaning of their KP_SPEC_* counterparts.
+ * Null tables per transcript and class (a call of a spectrum session): kp_spec_null's replicates,
+ * binned as kp_spec_coding bins.
+ *   kp_spec_coding_null  Transcripts, codons, classes and `splice` exactly as kp_spec_coding defines
+ *                    them; rates, scale, seed, contig_id, rep_first and n_reps exactly as
+ *                    kp_spec_null's.  counts[n_tx][n_reps][5]: counts[t][j][c] = the number of
+ *                    positions p that are a coding or essential splice position of transcript t and
+ *                    at which kp_spec_simulate with the same (seq, contig_id, rates, scale, seed) and
+ *                    replicate = rep_first + j draws a hit whose forward ALT a gives class c in
+ *                    kp_spec_coding_sites (p, a, t).  A hit at a position without a class (cls = -2)
+ *                    enters no column and is counted in the stats as `unclassed`.  A position whose
+ *                    window is invalid or leaves the contig draws nothing, so unlike kp_spec_coding
+ *                    no clipped centre is made up for on the host.  The result depends on (seed,
+ *                    contig_id, position, replicate), the model and transcript t only -- not on the
+ *                    other transcripts, on how replicates are batched, on the grid, knobs or arrival
+ *                    order: (rep_first = a, n_reps = b) equals columns a .. a + b - 1 of (0, a + b).
+ *                    Counts are integers, so the device result equals the host result bit for bit; a
+ *                    count is at most the transcript's positions, below 2^32, so uint32 cannot wrap.
+ *                    KP_E_STATE outside a session.  KP_E_ARG, checked on the host before any launch
+ *                    (counts is left untouched): whatever kp_spec_coding rejects about the transcript
+ *                    table and splice, and whatever kp_spec_null rejects about counts, rates, scale,
+ *                    n_reps and rep_first.  KP_E_NOMEM if the table and the staged records (32 bytes
+ *                    per position) do not fit the arena beside the lookup table, which stays where it
+ *                    was or is built again if the arena grew, as in kp_spec_null.
+ *   kp_spec_last_coding_null  figures of the session's last kp_spec_coding_null call; all but the
+ *                    times, passes and reps_per_pass are equal between the host and a device session.
+ * With ctx = NULL the call runs serially in the host session with the same per-pair functions.  On
+ * the device the work that does not depend on the replicate runs once: a stage kernel with one
+ * thread per (transcript, position) finds its segment or splice interval by a bounded binary search
+ * over host-computed dense offsets, reads its window, table entry and rates, and stores a 32-byte
+ * record -- the three integer thresholds of kp_spec_null (T2 = 0: draws nothing), the position and
+ * the class of each ALT slot -- at item base + index, so a transcript's records are contiguous and
+ * nothing is compacted.  A draw kernel then runs a persistent grid over (piece of at most 4,095
+ * records of one transcript, replicate chunk) units: records are wave-uniform, lanes hold
+ * consecutive replicates, the first Philox round runs once per record and the other nine once per
+ * lane, the five class counters of a lane are 12-bit fields of one 64-bit register, and each
+ * non-zero (transcript, replicate, class) leaves with one global atomic.  A chunk holds at most 256
+ * replicates, one per thread; with 128 or fewer the four waves split a piece's records.  More
+ * replicates take several passes over the records, never over the sequence.  Knobs, read at each
+ * call (every setting gives the same table): KP_CNULL_REPS caps the replicates per pass,
+ * KP_CNULL_GRID both grids. */
 typedef struct {
     uint64_t windows; /* valid windows inside the regions                                          */
     uint64_t hits;    /* mutations drawn                                                           */
@@ -642,6 +682,16 @@ typedef struct {
     double scan_ms;     /* device time of the scan kernel (HIP events; 0 on the host)              */
     uint32_t path;      /* 0 none or host, 1 LDS counters, 2 global atomics                        */
 } kp_spec_coding_stats;
+typedef struct {
+    uint64_t positions;     /* coding and essential splice positions, summed over the transcripts    */
+    uint64_t drawing;       /* ... among them with a valid window and c2 > 0                         */
+    uint64_t hits;          /* the sum of the table                                                  */
+    uint64_t unclassed;     /* hits at positions without a class, summed over the replicates         */
+    uint32_t passes;        /* replicate chunks the records were drawn in (1 on the host)            */
+    uint32_t reps_per_pass; /* replicates per chunk, the last one may hold fewer (n_reps on the host) */
+    double stage_ms;        /* device time of the stage kernel (HIP events; 0 on the host)           */
+    double draw_ms;         /* device time of the draw kernel (HIP events; 0 on the host)            */
+} kp_spec_coding_null_stats;
 int kp_seq_begin_typed(kp_ctx *ctx, int k, int fold);
 int kp_seq_sites_typed(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt,
                        uint64_t n_sites);
@@ -676,6 +726,11 @@ int kp_spec_coding_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint
                          uint32_t splice, const uint64_t *pos, const uint8_t *alt, const uint32_t *tx, uint64_t n_pairs,
                          int32_t *cls, int32_t *pid, uint32_t *codons);
 int kp_spec_last_coding(kp_ctx *ctx, kp_spec_coding_stats *out);
+int kp_spec_coding_null(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig_id, const uint64_t *seg_begin,
+                        const uint64_t *seg_end, uint64_t n_segs, const uint64_t *tx_first, const uint8_t *tx_strand,
+                        uint64_t n_tx, uint32_t splice, const double *rates, double scale, uint64_t seed, uint32_t rep_first,
+                        uint32_t n_reps, uint32_t *counts);
+int kp_spec_last_coding_null(kp_ctx *ctx, kp_spec_coding_null_stats *out);
 
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy

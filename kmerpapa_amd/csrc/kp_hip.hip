@@ -97,3 +97,4 @@
 #include "kp_sim.h"
 #include "kp_null.h"
 #include "kp_coding.h"
+#include "kp_cnull.h"

@@ -144,6 +144,7 @@ struct kp_spec_sess {
     kp_spec_sim_stats sim{};  // of the last kp_spec_simulate call (kp_sim.h)
     kp_spec_null_stats null{};  // of the last kp_spec_null call (kp_null.h)
     kp_spec_coding_stats coding{};  // of the last kp_spec_coding call (kp_coding.h)
+    kp_spec_coding_null_stats cnull{};  // of the last kp_spec_coding_null call (kp_cnull.h)
 };
 
 #define KP_SIDE_STREAMS 3

@@ -108,6 +108,12 @@ class KPSpecCodingStats(ctypes.Structure):
                 ("scan_ms", ctypes.c_double), ("path", ctypes.c_uint32)]
 
 
+class KPSpecCodingNullStats(ctypes.Structure):
+    _fields_ = [("positions", ctypes.c_uint64), ("drawing", ctypes.c_uint64), ("hits", ctypes.c_uint64),
+                ("unclassed", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("reps_per_pass", ctypes.c_uint32),
+                ("stage_ms", ctypes.c_double), ("draw_ms", ctypes.c_double)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
@@ -123,7 +129,8 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
            "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
            "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim",
-           "kp_spec_null", "kp_spec_last_null", "kp_spec_coding", "kp_spec_coding_sites", "kp_spec_last_coding"]
+           "kp_spec_null", "kp_spec_last_null", "kp_spec_coding", "kp_spec_coding_sites", "kp_spec_last_coding",
+           "kp_spec_coding_null", "kp_spec_last_coding_null"]
 
 
 def load():
@@ -241,6 +248,11 @@ def load():
             L.kp_spec_coding.argtypes = table + [vp, vp, vp, vp]
             L.kp_spec_coding_sites.argtypes = table + [vp, vp, vp, u64, vp, vp, vp]
             L.kp_spec_last_coding.argtypes = [vp, ctypes.POINTER(KPSpecCodingStats)]
+        if hasattr(L, "kp_spec_coding_null"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            L.kp_spec_coding_null.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, u32, vp, ctypes.c_double, u64, u32,
+                                              u32, vp]
+            L.kp_spec_last_coding_null.argtypes = [vp, ctypes.POINTER(KPSpecCodingNullStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -952,6 +964,37 @@ class _SpecCalls:
         st = KPSpecCodingStats()
         _check(load().kp_spec_last_coding(self._h, ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in KPSpecCodingStats._fields_}
+
+    def spec_coding_null(self, seq, transcripts, rates, seed, contig_id=0, rep_first=0, n_reps=1, scale=1.0, splice=2):
+        """The mutation count of every transcript by coding consequence in each of ``n_reps``
+        replicates of :meth:`spec_simulate`'s draw (kp_spec_coding_null): uint32 ``[m, n_reps, 5]``
+        (synonymous, missense, nonsense, stop-lost, essential splice).  Column ``j`` counts the
+        hits of replicate ``rep_first + j`` as :meth:`spec_coding_sites` classes them;
+        ``transcripts`` as :meth:`spec_coding`'s."""
+        seq, n = _seq_bytes(seq)
+        sb, se, first, strand = _transcript_arrays(transcripts)
+        m = strand.shape[0]
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != self._spec_P:
+            raise ValueError("one rate per pattern")
+        for name, v in (("seed", seed), ("contig_id", contig_id), ("rep_first", rep_first), ("n_reps", n_reps)):
+            if not 0 <= int(v) < (1 << 64 if name == "seed" else 1 << 32):
+                raise ValueError(f"{name} must be an unsigned {64 if name == 'seed' else 32}-bit integer")
+        shape = (m, int(n_reps), 5)
+        size = int(np.prod(shape, dtype=np.int64))
+        counts = np.zeros(max(size, 1), np.uint32)  # (never a null pointer)
+        _check(load().kp_spec_coding_null(self._h, _ptr(seq), n, ctypes.c_uint32(int(contig_id)), _ptr(sb), _ptr(se),
+                                          ctypes.c_uint64(sb.shape[0]), _ptr(first), _ptr(strand), ctypes.c_uint64(m),
+                                          ctypes.c_uint32(int(splice)), _ptr(r), ctypes.c_double(float(scale)),
+                                          ctypes.c_uint64(int(seed)), ctypes.c_uint32(int(rep_first)),
+                                          ctypes.c_uint32(int(n_reps)), _ptr(counts)))
+        return counts[:size].reshape(shape)
+
+    def spec_coding_null_stats(self):
+        """Figures of the session's last :meth:`spec_coding_null` call (kp_spec_last_coding_null) as a dict."""
+        st = KPSpecCodingNullStats()
+        _check(load().kp_spec_last_coding_null(self._h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in KPSpecCodingNullStats._fields_}
 
     def spec_end(self):
         """Close the session (kp_spec_end)."""

@@ -38,6 +38,12 @@ kp_coding.h).  The class of a (position, ALT) pair comes from the standard genet
 transcript's CDS (``--gtf`` or ``--cds-bed``); its rate is the model's, as ``sites`` reports it.
 ``consequences`` writes the class, codons and amino acids of given mutations, one line per site
 and transcript.
+
+``coding-null`` joins the two: the null distribution of the mutation count per transcript and
+class (``engine.Device.spec_coding_null``, kp_cnull.h).  Column ``j`` is exactly ``simulate
+--replicate F+j`` classified as ``coding --observed`` classifies it; each transcript gets, per class
+and for all classes and the loss-of-function ones together, the mean, variance and range of its
+simulated counts and, with ``--observed``, the observed count and empirical p-values.
 """
 import argparse
 import contextlib
@@ -450,6 +456,57 @@ def coding_rates(contigs, model, transcripts, splice=2, scale=1.0, by_type=False
     if by_type:
         out["expected_by_type"] = exp * float(scale)
     return out
+
+
+def _contig_coding_null(s, seq, txs, rates, seed, contig_id, first, replicates, scale, splice, budget, stats=None):
+    """One contig's table in batches of transcripts, and of replicates if need be, of at most
+    ``budget`` counters a call."""
+    m = len(txs)
+    rep_step = max(1, min(int(replicates), int(budget) // 5))
+    tx_step = max(1, int(budget) // (rep_step * 5))
+    out = np.zeros((m, replicates, 5), np.uint32)
+    for b in range(0, m, tx_step):
+        table = [(t.strand, t.segments) for t in txs[b:b + tx_step]]
+        for j in range(0, replicates, rep_step):
+            n = min(rep_step, replicates - j)
+            out[b:b + tx_step, j:j + n] = s.spec_coding_null(seq, table, rates, seed, contig_id, first + j, n, scale, splice)
+            if stats is not None:
+                st = s.spec_coding_null_stats()
+                for key in ("hits", "unclassed") + (("positions", "drawing") if j == 0 else ()):
+                    stats[key] = stats.get(key, 0) + st[key]
+    return out
+
+
+def coding_null_table(contigs, model, transcripts, seed, replicates, first=0, scale=1.0, splice=2, fold=True, host=False,
+                      budget=DEFAULT_BUDGET, stats=None):
+    """The null distribution of the mutation count per transcript and coding consequence
+    (``engine.Device.spec_coding_null``): ``{"counts": uint32 [T, replicates, 5], "status": int64
+    [T]}``, rows in the order of ``transcripts`` (``seqio.Transcript`` objects).  Column ``j``
+    holds, per transcript and class (:data:`CLASSES`), the hits :func:`simulate` draws with
+    ``replicate = first + j`` and the same seed, scale and genome, classed as
+    :func:`coding_sites` classes them: the contig enters the draw by its 0-based index in genome
+    order, exactly as there.  ``status`` as :func:`coding_rates`'; a skipped transcript's rows are
+    zero.  Batching by ``budget`` counters a call changes no result.  A dict ``stats`` gets
+    ``positions``, ``drawing``, ``hits`` and ``unclassed`` added up over the calls.  A contig whose
+    sequence is None must hold no usable transcript."""
+    replicates, first = int(replicates), int(first)
+    if replicates < 1 or first < 0 or first + replicates > 1 << 32:
+        raise ValueError("the replicates must be at least one and number below 2^32")
+    transcripts = list(transcripts)
+    counts = np.zeros((len(transcripts), replicates, 5), np.uint32)
+    per = {}
+    for i, t in enumerate(transcripts):
+        if t.length % 3 == 0:
+            per.setdefault(t.contig, []).append(i)
+    seen = set()
+    with session(model, fold, host) as s:
+        for contig_id, (name, seq) in enumerate(contigs):
+            seen.add(name)
+            if name in per:
+                counts[np.array(per[name])] = _contig_coding_null(s, seq, [transcripts[i] for i in per[name]], model.rates,
+                                                                  seed, contig_id, first, replicates, scale, splice, budget,
+                                                                  stats)
+    return {"counts": counts, "status": _usable(transcripts, seen)}
 
 
 def site_pairs(txs, pos):
@@ -889,6 +946,31 @@ def _check_splice(splice):
         raise ValueError("--splice must be 0..8")
 
 
+def _coding_observed(args, model, fold, host, report, txs, status, seqs):
+    """int64 ``[T, 5]``: the sites of ``args.observed`` per usable transcript and class (``cls >=
+    0``); ``seqs``: every contig of the genome by name."""
+    obs = np.zeros((len(txs), 5), np.int64)
+    raw = _matched_sites(args.observed, report)
+    per = {}
+    for i, t in enumerate(txs):
+        if status[i] == 0:
+            per.setdefault(t.contig, []).append(i)
+    outside = 0
+    with session(model, fold, host) as s:
+        for name, seq in seqs.items():
+            if name not in raw:
+                continue
+            pos, ref, alt = _keep_matching(seq, *raw[name], report)
+            own = [txs[i] for i in per.get(name, [])]
+            si, ti, cls, _, _ = coding_sites(s, seq, own, pos, alt, args.splice)
+            hit = cls >= 0
+            np.add.at(obs, (np.array(per.get(name, []), np.int64)[ti[hit]], cls[hit]), 1)
+            outside += pos.shape[0] - np.unique(si).shape[0]
+    report["unknown_contig"] = sum(len(v[0]) for name, v in raw.items() if name not in seqs)
+    report["observed_outside"] = outside
+    return obs
+
+
 def _run_coding(args, model, fold, host, report, out):
     _check_splice(args.splice)
     txs = _read_transcripts(args)
@@ -904,26 +986,7 @@ def _run_coding(args, model, fold, host, report, out):
     res = coding_rates(contigs(), model, txs, args.splice, args.scale, args.by_type, fold, host)
     status, other, exp = res["status"], res["other"], res["expected"]
     report.update(transcripts=T, skipped_length=int((status == 1).sum()), unknown_contig_transcripts=int((status == 2).sum()))
-    obs = np.zeros((T, 5), np.int64)
-    if args.observed:
-        raw = _matched_sites(args.observed, report)
-        per = {}
-        for i, t in enumerate(txs):
-            if status[i] == 0:
-                per.setdefault(t.contig, []).append(i)
-        outside = 0
-        with session(model, fold, host) as s:
-            for name, seq in seqs.items():
-                if name not in raw:
-                    continue
-                pos, ref, alt = _keep_matching(seq, *raw[name], report)
-                own = [txs[i] for i in per.get(name, [])]
-                si, ti, cls, _, _ = coding_sites(s, seq, own, pos, alt, args.splice)
-                hit = cls >= 0
-                np.add.at(obs, (np.array(per.get(name, []), np.int64)[ti[hit]], cls[hit]), 1)
-                outside += pos.shape[0] - np.unique(si).shape[0]
-        report["unknown_contig"] = sum(len(v[0]) for name, v in raw.items() if name not in seqs)
-        report["observed_outside"] = outside
+    obs = _coding_observed(args, model, fold, host, report, txs, status, seqs) if args.observed else np.zeros((T, 5), np.int64)
     tids = sorted(set(model.ptype.tolist()))
     kinds = [TYPES(False)[t] for t in tids]
     head = ["#name", "gene", "contig", "strand", "cds_bases"] + [f"opp_{c}" for c in CLASSES] + [f"exp_{c}" for c in CLASSES]
@@ -943,6 +1006,64 @@ def _run_coding(args, model, fold, host, report, out):
             tok += [repr(float(res["expected_by_type"][i, c, ty])) for c in range(5) for ty in tids]
         lines.append(" ".join(tok) + "\n")
     out.write("".join(lines))
+
+
+def _run_coding_null(args, model, fold, host, report, out):
+    _check_splice(args.splice)
+    R, first = args.replicates, args.first_replicate
+    if not 0 <= args.seed < 1 << 64:
+        raise ValueError("--seed must be an unsigned 64-bit integer")
+    if R < 1 or first < 0 or first + R > 1 << 32:
+        raise ValueError("--replicates must be at least 1, and --first-replicate + --replicates at most 2^32")
+    txs = _read_transcripts(args)
+    T = len(txs)
+    wanted = {t.contig for t in txs if t.length % 3 == 0}
+    seqs = {}  # every contig in genome order; the sequence of those a later step reads
+
+    def contigs():
+        for name, seq in seqio.read_genome(args.genome):
+            seqs[name] = seq if args.observed or name in wanted else None
+            yield name, seq
+
+    res = coding_rates(contigs(), model, txs, args.splice, args.scale, False, fold, host)
+    status, other, exp = res["status"], res["other"], res["expected"]
+    stats = {"positions": 0, "drawing": 0, "hits": 0, "unclassed": 0}
+    tab = coding_null_table(seqs.items(), model, txs, args.seed, R, first, args.scale, args.splice, fold, host,
+                            stats=stats)["counts"]
+    report.update(transcripts=T, skipped_length=int((status == 1).sum()), unknown_contig_transcripts=int((status == 2).sum()),
+                  **stats)
+    obs = _coding_observed(args, model, fold, host, report, txs, status, seqs) if args.observed else None
+    # a summary per column: the five classes, then all of them and nonsense + essential splice, summed per replicate
+    cols = CLASSES + ["total", "lof"]
+    sims = [tab[:, :, c] for c in range(5)] + [tab.sum(axis=2, dtype=np.uint32), tab[:, :, 2] + tab[:, :, 4]]
+    keys = ["mean", "var", "min", "max"] + (["p_upper", "p_lower"] if args.observed else [])
+    obs_cols, summary = [], []
+    for c, one in enumerate(sims):
+        ob = None
+        if args.observed:
+            ob = obs[:, c] if c < 5 else (obs.sum(axis=1) if c == 5 else obs[:, 2] + obs[:, 4])
+        obs_cols.append(ob)
+        summary.append(null_summary(one, ob) if T else {key: [] for key in keys})
+    head = ["#name", "gene", "contig", "strand", "cds_bases"] + [f"opp_{c}" for c in CLASSES] + [f"exp_{c}" for c in CLASSES]
+    for col in cols:
+        head += [f"sim_mean_{col}", f"sim_var_{col}", f"sim_min_{col}", f"sim_max_{col}"]
+        if args.observed:
+            head += [f"obs_{col}", f"p_upper_{col}", f"p_lower_{col}"]
+    lines = [" ".join(head) + "\n"]
+    for i, t in enumerate(txs):
+        tok = [t.name, t.gene if t.gene is not None else ".", t.contig, "+-"[t.strand], str(t.length)]
+        tok += [str(int(x)) for x in other[i, :5]] + [repr(float(x)) for x in exp[i]]
+        for c in range(len(cols)):
+            sm = summary[c]
+            tok += [repr(float(sm["mean"][i])), repr(float(sm["var"][i])), str(sm["min"][i]), str(sm["max"][i])]
+            if args.observed:
+                tok += [str(int(obs_cols[c][i])), repr(float(sm["p_upper"][i])), repr(float(sm["p_lower"][i]))]
+        lines.append(" ".join(tok) + "\n")
+    out.write("".join(lines))
+    if args.draws:
+        with open(args.draws, "w") as f:
+            f.write("".join(f"{t.name} {CLASSES[c]} " + " ".join(map(str, tab[i, :, c].tolist())) + "\n"
+                            for i, t in enumerate(txs) for c in range(5)))
 
 
 def _run_consequences(args, model, fold, host, report, out):
@@ -1090,6 +1211,19 @@ def get_parser():
     cod.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every expected count by X (default 1)")
     cod.add_argument("--observed", metavar="SITES", help="CHROM POS REF ALT lines to count per transcript and class")
     cod.add_argument("--by-type", action="store_true", help="The expected counts per class and mutation type of the model as well")
+    cnu = sub.add_parser("coding-null", help="per transcript and coding consequence: the null distribution of the "
+                                             "mutation count over many simulated sets, and empirical p-values")
+    applying(cnu)
+    annotated(cnu)
+    cnu.add_argument("--replicates", type=int, required=True, metavar="R", help="Number of simulated sets")
+    cnu.add_argument("--seed", type=int, required=True,
+                     help="Seed of the draws (0 .. 2^64 - 1): set j is `simulate --seed SEED --replicate F+j`")
+    cnu.add_argument("--first-replicate", type=int, default=0, metavar="F", help="Number of the first set (default 0)")
+    cnu.add_argument("--scale", type=float, default=1.0, metavar="X", help="Multiply every rate by X (default 1)")
+    cnu.add_argument("--observed", metavar="SITES",
+                     help="CHROM POS REF ALT lines to count per transcript and class as `coding --observed` does; adds "
+                          "obs_* and the empirical p_upper = (1 + #{sim >= obs}) / (R + 1) and p_lower (with <=)")
+    cnu.add_argument("--draws", metavar="FILE", help="Write the raw counts: one line per transcript and class, R integers")
     con = sub.add_parser("consequences", help="the class, codons and amino acids of given mutations, per transcript")
     applying(con)
     annotated(con)
@@ -1135,7 +1269,8 @@ def main(argv=None, host=False):
             model = Model.read(args.model)
             _check_fold(model, fold)
             run = {"regions": _run_regions, "track": _run_track, "sites": _run_sites, "simulate": _run_simulate,
-                   "null": _run_null, "coding": _run_coding, "consequences": _run_consequences}[args.command]
+                   "null": _run_null, "coding": _run_coding, "coding-null": _run_coding_null,
+                   "consequences": _run_consequences}[args.command]
             streamed = args.command in ("track", "simulate")  # (written contig by contig)
             try:
                 if streamed and args.output != "-":

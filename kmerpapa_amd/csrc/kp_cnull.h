@@ -225,7 +225,7 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
                         uint32_t n_reps, uint32_t *counts) {
     const char *who = "kp_spec_coding_null";
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig(who, s, seq, n);
+    int rc = scan_check_contig(who, s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (!counts) return fail(KP_E_ARG, "kp_spec_coding_null: null counts");
     if (!rates) return fail(KP_E_ARG, "kp_spec_coding_null: null rates");
@@ -368,7 +368,7 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
         const size_t b_items = g_up(items.size() * sizeof(kp_cd_rec)), b_rec0 = g_up(rec0.size() * 8);
         const size_t b_pieces = g_up(pieces.size() * sizeof(kp_cn_piece));
         uint8_t *d_seq = nullptr;
-        if ((rc = pred_upload_contig(c, who, seq, n, b_items + b_rec0 + b_pieces, &d_seq))) return rc;
+        if ((rc = scan_upload(c, who, seq, n, {}, b_items + b_rec0 + b_pieces, &d_seq, nullptr))) return rc;
         kp_cd_rec *d_items = (kp_cd_rec *)c->seq_in.take(b_items);
         uint64_t *d_rec0 = (uint64_t *)c->seq_in.take(b_rec0);
         kp_cn_piece *d_pieces = (kp_cn_piece *)c->seq_in.take(b_pieces);
@@ -377,13 +377,6 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
         KP_HIP(hipMemcpyAsync(d_rec0, rec0.data(), rec0.size() * 8, hipMemcpyHostToDevice, st));
         KP_HIP(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(kp_cn_piece), hipMemcpyHostToDevice, st));
         KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
-        const long grid_env = env_int("KP_CNULL_GRID", 0);
-        // persistent grids: eight workgroups without LDS are resident per compute unit
-        auto grid_of = [&](uint64_t units) {
-            uint64_t grid = std::min<uint64_t>(units, (uint64_t)c->cus * 8);
-            if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
-            return grid;
-        };
         kp_cn_sargs S;
         S.seq = d_seq;
         S.n = n;
@@ -401,7 +394,7 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
         S.scale = scale;
         S.recs = d_recs;
         S.stat = d_stat;
-        const uint64_t s_blocks = (n_recs + KP_CN_THREADS - 1) / KP_CN_THREADS, s_grid = grid_of(s_blocks);
+        const uint64_t s_blocks = (n_recs + KP_CN_THREADS - 1) / KP_CN_THREADS, s_grid = scan_grid(c, s_blocks, 8, "KP_CNULL_GRID");  // no LDS
         const uint64_t s_steps = (s_blocks + s_grid - 1) / s_grid;
         if (s_steps >= (1ull << 32)) return fail(KP_E_ARG, "kp_spec_coding_null: too many positions for this grid");
         S.steps = (uint32_t)s_steps;
@@ -417,15 +410,13 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
         D.passes = passes;
         D.counts = d_counts;
         D.stat = d_stat;
-        const uint64_t d_grid = grid_of(D.n_units);
+        const uint64_t d_grid = scan_grid(c, D.n_units, 8, "KP_CNULL_GRID");
         D.steps = (D.n_units + d_grid - 1) / d_grid;
-        KP_HIP(hipEventRecord(c->ev[0], st));
+        if ((rc = scan_mark(c, 0))) return rc;
         hipLaunchKernelGGL(kp_cnull_stage_kernel, dim3((unsigned)s_grid), dim3(KP_CN_THREADS), 0, st, S);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
+        if ((rc = scan_launched(c, 1))) return rc;
         hipLaunchKernelGGL(kp_cnull_draw_kernel, dim3((unsigned)d_grid), dim3(KP_CN_THREADS), 0, st, D);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[2], st));
+        if ((rc = scan_launched(c, 2))) return rc;
     }
     unsigned long long stat[2] = {0, 0};
     KP_HIP(hipMemcpyAsync(counts, d_counts, n_cnt * 4, hipMemcpyDeviceToHost, st));
@@ -433,9 +424,9 @@ int kp_spec_coding_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t cont
     KP_HIP(hipStreamSynchronize(st));
     if (n_recs) {
         float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
         s->cnull.stage_ms = ms;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
+        if ((rc = scan_elapsed(c, 1, 2, &ms))) return rc;
         s->cnull.draw_ms = ms;
     }
     uint64_t hits = 0;

@@ -458,7 +458,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
                    uint64_t n_segs, const uint64_t *tx_first, const uint8_t *tx_strand, uint64_t n_tx, uint32_t splice,
                    const double *rates, uint64_t *hist, uint64_t *other, double *expected) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_coding", s, seq, n);
+    int rc = scan_check_contig("kp_spec_coding", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (n_tx && !other) return fail(KP_E_ARG, "kp_spec_coding: null counters");
     if (rates && n_tx && !expected) return fail(KP_E_ARG, "kp_spec_coding: rates without a place for the sums");
@@ -477,13 +477,9 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
     const uint32_t P = (uint32_t)s->pats.size();
     const uint32_t mask = (uint32_t)(s->cells - 1);
     const uint64_t n_rows = n_tx * KP_CD_CLASSES;
-    // centres whose window lies inside the contig: [lo, hi)
-    const uint64_t lo = (uint64_t)(k / 2), hi = n >= (uint64_t)k ? n - (uint64_t)k + lo + 1 : lo;
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     const uint64_t *sb = seg_begin, *se = seg_end;
-    auto pieces = [&](uint64_t b, uint64_t e) {  // work items of the positions [b, e)
-        b = std::max(b, lo), e = std::min(e, hi);
-        return e > b ? (e - b + KP_S_TILE - 1) / KP_S_TILE : 0;
-    };
     if (!c) {
         std::vector<uint64_t> rows;
         try {
@@ -503,7 +499,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
                     kp_cd_codon_at(seq, sb, se, t0, t1, e, g, sj0[e] + (g - sb[e]), x, &i);
                     cd_host_position(s, seq, n, g, false, x, i, tx_strand[t], rows.data(), o);
                 }
-                n_items += pieces(sb[e], se[e]);
+                n_items += scan_pieces(sb[e], se[e], lo, hi);
                 positions += se[e] - sb[e];
                 if (e + 1 < t1) {
                     uint64_t iv[4];
@@ -511,7 +507,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
                     for (int v = 0; v < 4; v += 2) {
                         for (uint64_t g = iv[v]; g < iv[v + 1]; ++g)
                             cd_host_position(s, seq, n, g, true, nullptr, 0, tx_strand[t], rows.data(), o);
-                        n_items += pieces(iv[v], iv[v + 1]);
+                        n_items += scan_pieces(iv[v], iv[v + 1], lo, hi);
                         positions += iv[v + 1] - iv[v];
                     }
                 }
@@ -546,11 +542,6 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
     uint64_t positions = 0;
     try {
         h_other.assign(n_tx * KP_CD_OTHER, 0);
-        auto cut = [&](uint64_t b, uint64_t e, uint32_t rec) {
-            b = std::max(b, lo), e = std::min(e, hi);
-            for (uint64_t f = b; f < e; f += KP_S_TILE)
-                items.push_back(kp_p_item{(uint32_t)f, (uint32_t)std::min<uint64_t>(KP_S_TILE, e - f), rec});
-        };
         // the centres of [b, e) whose window leaves the contig: the host's share
         auto clipped = [&](uint64_t b, uint64_t e, auto &&fn) {
             for (uint64_t g = b; g < std::min(e, lo); ++g) fn(g);
@@ -570,7 +561,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
                         kp_cd_near(seq, sb, se, t0, t1, e, se[e] - 1, 1) << 6 |
                         kp_cd_near(seq, sb, se, t0, t1, e, se[e] - 1, 2) << 9;
                 recs.push_back(r);
-                cut(sb[e], se[e], (uint32_t)(recs.size() - 1));
+                scan_cut(items, sb[e], se[e], lo, hi, (uint32_t)(recs.size() - 1));
                 positions += se[e] - sb[e];
                 clipped(sb[e], se[e], [&](uint64_t g) {
                     uint32_t x[3], i = 0;
@@ -588,7 +579,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
                         r.flags = (tx_strand[t] ? KP_CD_F_STRAND : 0u) | KP_CD_F_SPLICE;
                         r.ctx = 0;
                         recs.push_back(r);
-                        cut(iv[v], iv[v + 1], (uint32_t)(recs.size() - 1));
+                        scan_cut(items, iv[v], iv[v + 1], lo, hi, (uint32_t)(recs.size() - 1));
                         positions += iv[v + 1] - iv[v];
                         clipped(iv[v], iv[v + 1],
                                 [&](uint64_t g) { cd_host_position(s, seq, n, g, true, nullptr, 0, tx_strand[t], nullptr, o); });
@@ -617,23 +608,17 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
     KP_HIP(hipMemsetAsync(d_hist, 0, cnts * 8, st));
     KP_HIP(hipMemsetAsync(d_other, 0, n_tx * KP_CD_OTHER * 8, st));
     if (!items.empty()) {
-        const size_t b_items = g_up(items.size() * sizeof(kp_p_item)), b_recs = g_up(recs.size() * sizeof(kp_cd_rec));
-        const size_t b_tab = g_up(sizeof h_tab);
+        const size_t b_recs = g_up(recs.size() * sizeof(kp_cd_rec)), b_tab = g_up(sizeof h_tab);
         uint8_t *d_seq = nullptr;
-        if ((rc = pred_upload_contig(c, "kp_spec_coding", seq, n, b_items + b_recs + b_tab, &d_seq))) return rc;
-        kp_p_item *d_items = (kp_p_item *)c->seq_in.take(b_items);
+        kp_p_item *d_items = nullptr;
+        if ((rc = scan_upload(c, "kp_spec_coding", seq, n, items, b_recs + b_tab, &d_seq, &d_items))) return rc;
         kp_cd_rec *d_recs = (kp_cd_rec *)c->seq_in.take(b_recs);
         uint32_t *d_tab = (uint32_t *)c->seq_in.take(b_tab);
         if ((rc = c->seq_in.check("kp_spec_coding"))) return rc;
-        KP_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(kp_p_item), hipMemcpyHostToDevice, st));
         KP_HIP(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(kp_cd_rec), hipMemcpyHostToDevice, st));
         KP_HIP(hipMemcpyAsync(d_tab, h_tab, sizeof h_tab, hipMemcpyHostToDevice, st));
         const size_t lds_bytes = 4u * KP_CD_TAB_WORDS + (lds ? (size_t)KP_CD_CLASSES * P * 4 : 0);
-        // a persistent grid: as many workgroups as are resident at once
-        const int per_cu = lds_bytes <= 16u * 1024u ? 8 : (lds_bytes <= 40u * 1024u ? 4 : 2);
-        uint64_t grid = std::min<uint64_t>(items.size(), (uint64_t)c->cus * per_cu);
-        const long grid_env = env_int("KP_CODING_GRID", 0);
-        if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
+        const uint64_t grid = scan_grid(c, items.size(), scan_per_cu(lds_bytes), "KP_CODING_GRID");
         kp_cd_args A;
         A.seq = d_seq;
         A.n = (uint32_t)n;
@@ -652,13 +637,12 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
         if (lds_bytes > 65536)
             KP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kp_coding_scan_kernel<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        KP_HIP(hipEventRecord(c->ev[0], st));
+        if ((rc = scan_mark(c, 0))) return rc;
         if (lds)
             hipLaunchKernelGGL((kp_coding_scan_kernel<true>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
         else
             hipLaunchKernelGGL((kp_coding_scan_kernel<false>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
+        if ((rc = scan_launched(c, 1))) return rc;
     }
     if (rates) {
         KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
@@ -675,7 +659,7 @@ int kp_spec_coding(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *se
     KP_HIP(hipStreamSynchronize(st));
     if (!items.empty()) {
         float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
         s->coding.scan_ms = ms;
         s->coding.path = lds ? 1u : 2u;
     }
@@ -696,7 +680,7 @@ int kp_spec_coding_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64
                          uint32_t splice, const uint64_t *pos, const uint8_t *alt, const uint32_t *tx, uint64_t n_pairs,
                          int32_t *cls, int32_t *pid, uint32_t *codons) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_coding_sites", s, seq, n);
+    int rc = scan_check_contig("kp_spec_coding_sites", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     std::vector<uint64_t> sj0;
     uint32_t iters = 0;
@@ -737,7 +721,7 @@ int kp_spec_coding_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64
     uint8_t *d_seq = nullptr;
     const size_t more = 3 * g_up(n_segs * 8) + g_up((n_tx + 1) * 8) + g_up(n_tx) + g_up(n_pairs * 8) + g_up(n_pairs) +
                         g_up(n_pairs * 4);
-    if ((rc = pred_upload_contig(c, "kp_spec_coding_sites", seq, n, more, &d_seq))) return rc;
+    if ((rc = scan_upload(c, "kp_spec_coding_sites", seq, n, {}, more, &d_seq, nullptr))) return rc;
     uint64_t *d_sb = (uint64_t *)c->seq_in.take(n_segs * 8);
     uint64_t *d_se = (uint64_t *)c->seq_in.take(n_segs * 8);
     uint64_t *d_sj = (uint64_t *)c->seq_in.take(n_segs * 8);

@@ -36,7 +36,7 @@
 //                      streaming scan with a rolling window per thread and a histogram in LDS
 //                      counters (k <= 7) or global 64-bit atomics; one thread per site
 //   kp_pred_*        a fitted partition taken back to the genome (kp_pred.h): a lookup table from
-//                      k-mer code to pattern, the kp_seq roll with one gather per window, and
+//                      k-mer code to pattern, the kp_seq roll in batches (kp_scan.h) with one gather per window, and
 //                      per-region pattern histograms in LDS counters or global 64-bit atomics
 //   kp_spec_*        every mutation type's partition in one pass (kp_spec.h): a table of 16-byte
 //                      entries (one pattern per ALT slot), the kp_pred roll with one gather and up
@@ -63,6 +63,8 @@
 //   kp_math.h      kp_math_*
 //   kp_allk.h, kp_greedy.h + kp_greedy_api.h, kp_apply.h   the other scores with their drivers
 //   kp_seq.h       the sequence scan, the sites kernel and the kp_seq_* sessions
+//   kp_scan.h      what the genome scans below share: the aligned loads and the batch roll on the device,
+//                  items, region check, uploads, table arena and timed launch on the host
 //   kp_pred.h      the prediction scan, track and sites kernels and the kp_pred_* sessions
 //   kp_spec.h      the spectrum table, scan, track and sites kernels, the kp_spec_* sessions and
 //                  typed site counting
@@ -92,6 +94,7 @@
 #include "kp_dump.h"
 #include "kp_math.h"
 #include "kp_seq.h"
+#include "kp_scan.h"
 #include "kp_pred.h"
 #include "kp_spec.h"
 #include "kp_sim.h"

@@ -217,7 +217,7 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
                  const uint64_t *reg_end, uint64_t n_regions, const double *rates, double scale, uint64_t seed,
                  uint32_t rep_first, uint32_t n_reps, int by_type, uint32_t *counts) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_null", s, seq, n);
+    int rc = scan_check_contig("kp_spec_null", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (!counts) return fail(KP_E_ARG, "kp_spec_null: null counts");
     if (!rates) return fail(KP_E_ARG, "kp_spec_null: null rates");
@@ -228,9 +228,7 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
         return fail(KP_E_ARG, "kp_spec_null: replicates " + std::to_string(rep_first) + " .. " +
                                   std::to_string((uint64_t)rep_first + n_reps - 1) + " go past 2^32 - 1");
     if ((rc = sim_check_rates(s, rates, scale))) return rc;
-    for (uint64_t r = 0; r < n_regions; ++r)
-        if (reg_begin[r] > reg_end[r] || reg_end[r] > n)
-            return fail(KP_E_ARG, "kp_spec_null: region " + std::to_string(r) + " has begin > end or lies outside the contig");
+    if ((rc = scan_check_regions("kp_spec_null", n, reg_begin, reg_end, n_regions, false))) return rc;
     s->null = kp_spec_null_stats{};
     if (!n_regions) return KP_OK;
     const int k = s->k;
@@ -238,14 +236,14 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
     const uint32_t mask = (uint32_t)(s->cells - 1);
     const uint32_t NT = by_type ? (uint32_t)KP_SP_TYPES : 1u;
     const size_t n_cnt = (size_t)n_regions * n_reps * NT;
-    // centres whose window lies inside the contig: [lo, hi)
-    const uint64_t lo = (uint64_t)(k / 2), hi = n >= (uint64_t)k ? n - (uint64_t)k + lo + 1 : lo;
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     if (!c) {
         memset(counts, 0, n_cnt * 4);
         uint64_t windows = 0, drawing = 0, hits = 0, n_items = 0;
         for (uint64_t r = 0; r < n_regions; ++r) {
             const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            if (e > b) n_items += (e - b + KP_S_TILE - 1) / KP_S_TILE;
+            n_items += scan_pieces(reg_begin[r], reg_end[r], lo, hi);
             uint32_t *row = counts + r * n_reps * NT;
             for (uint64_t p = b; p < e; ++p) {
                 uint32_t code = 0;
@@ -284,11 +282,7 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
     s->null.reps_per_pass = chunk;
     std::vector<kp_p_item> items;
     try {
-        for (uint64_t r = 0; r < n_regions; ++r) {
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            for (uint64_t f = b; f < e; f += KP_S_TILE)
-                items.push_back(kp_p_item{(uint32_t)f, (uint32_t)std::min<uint64_t>(KP_S_TILE, e - f), (uint32_t)r});
-        }
+        for (uint64_t r = 0; r < n_regions; ++r) scan_cut(items, reg_begin[r], reg_end[r], lo, hi, (uint32_t)r);
     } catch (const std::bad_alloc &) {
         return fail(KP_E_NOMEM, "kp_spec_null: the work items do not fit host memory");
     }
@@ -304,12 +298,9 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
     KP_HIP(hipMemsetAsync(d_counts, 0, n_cnt * 4, st));
     KP_HIP(hipMemsetAsync(d_stat, 0, 16, st));
     if (n_items) {
-        const size_t b_items = g_up(n_items * sizeof(kp_p_item));
         uint8_t *d_seq = nullptr;
-        if ((rc = pred_upload_contig(c, "kp_spec_null", seq, n, b_items, &d_seq))) return rc;
-        kp_p_item *d_items = (kp_p_item *)c->seq_in.take(b_items);
-        if ((rc = c->seq_in.check("kp_spec_null"))) return rc;
-        KP_HIP(hipMemcpyAsync(d_items, items.data(), n_items * sizeof(kp_p_item), hipMemcpyHostToDevice, st));
+        kp_p_item *d_items = nullptr;
+        if ((rc = scan_upload(c, "kp_spec_null", seq, n, items, 0, &d_seq, &d_items))) return rc;
         KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
         kp_nl_args A;
         A.seq = d_seq;
@@ -329,18 +320,14 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
         A.passes = passes;
         A.counts = d_counts;
         A.stat = d_stat;
-        // a persistent grid: two workgroups of 62 KB of LDS are resident per compute unit
-        uint64_t grid = std::min<uint64_t>(A.n_units, (uint64_t)c->cus * 2);
-        const long grid_env = env_int("KP_NULL_GRID", 0);
-        if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
+        const uint64_t grid = scan_grid(c, A.n_units, 2, "KP_NULL_GRID");  // 62 KB of LDS per workgroup
         A.steps = (A.n_units + grid - 1) / grid;
-        KP_HIP(hipEventRecord(c->ev[0], st));
+        if ((rc = scan_mark(c, 0))) return rc;
         if (by_type)
             hipLaunchKernelGGL((kp_null_kernel<true>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
         else
             hipLaunchKernelGGL((kp_null_kernel<false>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
+        if ((rc = scan_launched(c, 1))) return rc;
     }
     unsigned long long stat[2] = {0, 0};
     KP_HIP(hipMemcpyAsync(counts, d_counts, n_cnt * 4, hipMemcpyDeviceToHost, st));
@@ -348,7 +335,7 @@ int kp_spec_null(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, 
     KP_HIP(hipStreamSynchronize(st));
     if (n_items) {
         float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
         s->null.null_ms = ms;
     }
     uint64_t hits = 0;

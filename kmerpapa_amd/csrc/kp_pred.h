@@ -2,8 +2,10 @@
 // by kp_hip.hip.  Semantics: include/kmerpapa_hip.h.
 //
 // Windows, validity, the centre and folding are kp_seq.h's (kp_s_class / kp_s_step / kp_s_code),
-// matching is kp_apply.h's (kp_a_onehot / kp_a_match).  Counts are integers and `expected` is a
-// float64 sum in pattern order, so a device session equals the host session bit for bit.
+// matching is kp_apply.h's (kp_a_onehot / kp_a_match), the aligned loads, the batched roll and the
+// host's items, region check, uploads, arena and timed launch are kp_scan.h's.  Counts are integers
+// and `expected` is a float64 sum in pattern order, so a device session equals the host session
+// bit for bit.
 //
 //   kp_pred_lut_kernel    one k-mer code per thread against every pattern (staged through LDS in
 //                         tiles, as kp_apply_assign stages them): lut[code] = the first and, the
@@ -34,12 +36,11 @@
 
 #include "kp_apply.h"
 #include "kp_rt.h"
+#include "kp_scan.h"
 #include "kp_seq.h"
 
 #define KP_P_LDS_P 16384   // most patterns with LDS counters: 64 KiB of uint32, two workgroups per CU
 #define KP_P_LUT_TILE 1024 // patterns per LDS tile of the table build
-#define KP_P_BATCH 8       // bytes of the roll whose gathers are issued together
-#define KP_P_ROW 257       // the track kernel's LDS row: KP_S_THREADS + 1, so a thread's slots spread over the banks
 #define KP_P_NONE (-1)
 #define KP_P_INVALID (-2)
 
@@ -65,10 +66,6 @@ __host__ __device__ inline bool kp_p_window(const uint8_t *seq, uint64_t n, uint
     *code = kp_s_code(w, k, fold);
     return w.valid == (uint32_t)k;
 }
-
-struct kp_p_item {
-    uint32_t first, count, region;  // centres [first, first + count) of the region's row
-};
 
 struct kp_p_args {
     const uint8_t *seq;      // the contig, KP_S_PAD readable bytes past its end
@@ -116,25 +113,6 @@ __global__ void __launch_bounds__(256) kp_pred_lut_kernel(const uint64_t *__rest
     if (code < cells) lut[code] = found;
 }
 
-// the four aligned 16-byte words that hold bytes [s0, s0 + len) of the contig, len <= 46; a thread
-// with len = 0 loads nothing: its s0 may lie far past the contig.  With len > 0, s0 + len <= n,
-// so every word loaded begins before n and ends before n + 15 < n + KP_S_PAD.
-__device__ inline void kp_p_load(const uint8_t *seq, uint64_t s0, uint32_t len, uint32_t d[16], uint32_t *off,
-                                 uint32_t *end) {
-    const uint64_t a = s0 & ~(uint64_t)15;
-    *off = (uint32_t)(s0 - a);
-    *end = *off + len;  // <= 15 + 32 + 14
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint4 w = make_uint4(0, 0, 0, 0);
-        if (len && 16u * q < *end) w = *reinterpret_cast<const uint4 *>(seq + a + 16u * q);
-        d[4 * q] = w.x;
-        d[4 * q + 1] = w.y;
-        d[4 * q + 2] = w.z;
-        d[4 * q + 3] = w.w;
-    }
-}
-
 template <bool LDS>
 __global__ void __launch_bounds__(KP_S_THREADS) kp_pred_scan_kernel(kp_p_args A) {
     extern __shared__ uint32_t kp_p_cnt[];  // [P] with LDS
@@ -161,15 +139,7 @@ __global__ void __launch_bounds__(KP_S_THREADS) kp_pred_scan_kernel(kp_p_args A)
             uint32_t code[KP_P_BATCH];
             bool has[KP_P_BATCH];
             int32_t p[KP_P_BATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < KP_P_BATCH; ++q) {
-                const uint32_t j = jb + q;
-                if (j >= off && j < end) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), A.mask, top);
-                const bool full = j >= full0 && j < end;
-                has[q] = full && w.valid >= (uint32_t)k;
-                inv += full && !has[q];
-                code[q] = kp_s_code(w, k, A.fold);
-            }
+            kp_scan_batch(w, d, jb, off, end, full0, k, A.fold, A.mask, top, code, has, inv);
 #pragma unroll
             for (uint32_t q = 0; q < KP_P_BATCH; ++q) p[q] = has[q] ? A.lut[code[q]] : KP_P_INVALID;
 #pragma unroll
@@ -225,19 +195,14 @@ __global__ void __launch_bounds__(KP_S_THREADS) kp_pred_track_kernel(kp_p_targs 
         kp_p_load(A.seq, nc ? cb - (uint32_t)h : 0u, nc ? nc + (uint32_t)k - 1u : 0u, d, &off, &end);
         const uint32_t full0 = off + (uint32_t)k - 1u;
         const uint32_t slot0 = nc ? (uint32_t)(cb - c0) : 0u;  // slot of the first window: byte j fills slot0 + j - full0
+        uint32_t inv = 0;  // (not reported: the slots of invalid windows keep their -2)
         kp_s_win w{0u, 0u, 0u};
 #pragma unroll
         for (uint32_t jb = 0; jb < 64; jb += KP_P_BATCH) {
             uint32_t code[KP_P_BATCH];
             bool has[KP_P_BATCH];
             int32_t p[KP_P_BATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < KP_P_BATCH; ++q) {
-                const uint32_t j = jb + q;
-                if (j >= off && j < end) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), A.mask, top);
-                has[q] = j >= full0 && j < end && w.valid >= (uint32_t)k;
-                code[q] = kp_s_code(w, k, A.fold);
-            }
+            kp_scan_batch(w, d, jb, off, end, full0, k, A.fold, A.mask, top, code, has, inv);
 #pragma unroll
             for (uint32_t q = 0; q < KP_P_BATCH; ++q) p[q] = has[q] ? A.lut[code[q]] : KP_P_INVALID;
 #pragma unroll
@@ -297,68 +262,20 @@ static thread_local kp_pred_sess g_pred_host;
 
 static kp_pred_sess *pred_sess(kp_ctx *c) { return c ? &c->pred : &g_pred_host; }
 
-static int pred_check_contig(const std::string &w, const kp_pred_sess *s, const uint8_t *seq, uint64_t n) {
-    if (!s->active) return fail(KP_E_STATE, w + ": no session (kp_pred_begin first)");
-    if (n && !seq) return fail(KP_E_ARG, w + ": null sequence");
-    if (n >= (1ull << 32)) return fail(KP_E_ARG, w + ": a contig of 2^32 bases or more");
-    return KP_OK;
-}
-
-// The arena of a device session laid out for one call: the lookup table first, then `extra`
-// bytes the caller takes.  Grows the arena if it has to -- against free memory minus 2 GiB -- and
-// then, or after a failed growth, builds the table again.
+// scan_arena for the table of 4-byte entries: the table first, then `extra` bytes the caller takes
 static int pred_arena(kp_ctx *c, const char *who, size_t extra) {
     kp_pred_sess *s = &c->pred;
     const uint32_t P = (uint32_t)s->pats.size();
-    const size_t b_lut = g_up((size_t)s->cells * 4), b_pats = g_up((size_t)P * 8);
-    const size_t need = b_lut + std::max(extra, b_pats);
-    if (need > c->arena.bytes) {
-        size_t fr = 0, tot = 0;
-        KP_HIP(hipMemGetInfo(&fr, &tot));
-        if (need + (2ull << 30) > fr + c->arena.bytes)
-            return fail(KP_E_NOMEM, std::string(who) + ": the lookup table of " + std::to_string(s->k) +
-                                        "-mers and this call's buffers need " + std::to_string(need >> 20) +
-                                        " MiB of device memory, " + std::to_string((fr + c->arena.bytes) >> 20) +
-                                        " MiB are free (2 GiB stay free)");
-        s->lut_ok = false;
-    }
-    int rc = c->arena.reserve(who, need);
-    if (rc) return rc;
-    s->d_lut = (int32_t *)c->arena.take((size_t)s->cells * 4);
-    if (!s->lut_ok) {
+    return scan_arena(c, s, who, "lookup", 4, g_up((size_t)P * 8), extra, [&]() -> int {
         uint64_t *d_pats = (uint64_t *)c->arena.take((size_t)P * 8);
-        if ((rc = c->arena.check(who))) return rc;
-        hipStream_t st = c->stream;
-        KP_HIP(hipMemcpyAsync(d_pats, s->pats.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
-        KP_HIP(hipEventRecord(c->ev[0], st));
-        hipLaunchKernelGGL(kp_pred_lut_kernel, dim3((unsigned)((s->cells + 255) / 256)), dim3(256), 0, st, d_pats, P, s->k,
-                           s->fold, (uint32_t)s->cells, s->d_lut);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
-        KP_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        s->st.lut_ms = ms;
-        s->lut_ok = true;
-        c->arena.used = b_lut;  // the staged patterns are done with
-    }
-    return KP_OK;
-}
-
-// the contig on the device, in the allocation kp_seq_scan uses; `more` bytes follow it
-static int pred_upload_contig(kp_ctx *c, const char *who, const uint8_t *seq, uint64_t n, size_t more, uint8_t **d_seq) {
-    int rc = c->seq_in.reserve(who, g_up(n + KP_S_PAD) + more);
-    if (rc) return rc;
-    *d_seq = (uint8_t *)c->seq_in.take(n + KP_S_PAD);
-    if (n) KP_HIP(hipMemcpyAsync(*d_seq, seq, n, hipMemcpyHostToDevice, c->stream));
-    return KP_OK;
-}
-
-static uint64_t pred_grid(kp_ctx *c, uint64_t n_items, int per_cu) {
-    uint64_t grid = std::min<uint64_t>(n_items, (uint64_t)c->cus * per_cu);
-    const long grid_env = env_int("KP_PRED_GRID", 0);
-    if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
-    return grid;
+        int rc = c->arena.check(who);
+        if (rc) return rc;
+        KP_HIP(hipMemcpyAsync(d_pats, s->pats.data(), (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = scan_mark(c, 0))) return rc;
+        hipLaunchKernelGGL(kp_pred_lut_kernel, dim3((unsigned)((s->cells + 255) / 256)), dim3(256), 0, c->stream, d_pats, P,
+                           s->k, s->fold, (uint32_t)s->cells, s->d_lut);
+        return scan_launched(c, 1);
+    });
 }
 
 // No two patterns share a k-mer.  A few patterns: every pair.  Many: every pattern's k-mers are
@@ -458,20 +375,18 @@ int kp_pred_begin(kp_ctx *c, int k, int fold, const uint64_t *patterns, uint32_t
 int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
                     uint64_t n_regions, const double *rates, uint64_t *hist, uint64_t *other, double *expected) {
     kp_pred_sess *s = pred_sess(c);
-    int rc = pred_check_contig("kp_pred_regions", s, seq, n);
+    int rc = scan_check_contig("kp_pred_regions", s->active, seq, n, "kp_pred_begin");
     if (rc) return rc;
     if (n_regions >= (1ull << 32)) return fail(KP_E_ARG, "kp_pred_regions: 2^32 regions or more in one call");
     if (n_regions && (!reg_begin || !reg_end || !other)) return fail(KP_E_ARG, "kp_pred_regions: null regions or counters");
     if (rates && n_regions && !expected) return fail(KP_E_ARG, "kp_pred_regions: rates without a place for the sums");
-    for (uint64_t r = 0; r < n_regions; ++r)
-        if (reg_begin[r] > reg_end[r] || reg_end[r] > n)
-            return fail(KP_E_ARG, "kp_pred_regions: region " + std::to_string(r) + " has begin > end or lies outside the contig");
+    if ((rc = scan_check_regions("kp_pred_regions", n, reg_begin, reg_end, n_regions, false))) return rc;
     if (!n_regions) return KP_OK;
     const int k = s->k;
     const uint32_t P = (uint32_t)s->pats.size();
     const uint32_t mask = (uint32_t)(s->cells - 1);
-    // centres whose window lies inside the contig: [lo, hi)
-    const uint64_t lo = (uint64_t)(k / 2), hi = n >= (uint64_t)k ? n - (uint64_t)k + lo + 1 : lo;
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     uint64_t n_items = 0;
     if (!c) {
         std::vector<uint64_t> row;
@@ -495,8 +410,7 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
                         ++none;
                 }
             }
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            if (e > b) n_items += (e - b + KP_S_TILE - 1) / KP_S_TILE;
+            n_items += scan_pieces(reg_begin[r], reg_end[r], lo, hi);
             other[2 * r] = none;
             other[2 * r + 1] = inv;
             s->st.unmatched += none;
@@ -522,12 +436,8 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     std::vector<uint64_t> off_contig;  // per region: centres outside [lo, hi)
     try {
         off_contig.resize(n_regions);
-        for (uint64_t r = 0; r < n_regions; ++r) {
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            off_contig[r] = reg_end[r] - reg_begin[r] - (e > b ? e - b : 0);
-            for (uint64_t f = b; f < e; f += KP_S_TILE)
-                items.push_back(kp_p_item{(uint32_t)f, (uint32_t)std::min<uint64_t>(KP_S_TILE, e - f), (uint32_t)r});
-        }
+        for (uint64_t r = 0; r < n_regions; ++r)
+            off_contig[r] = reg_end[r] - reg_begin[r] - scan_cut(items, reg_begin[r], reg_end[r], lo, hi, (uint32_t)r);
     } catch (const std::bad_alloc &) {
         return fail(KP_E_NOMEM, "kp_pred_regions: the work items do not fit host memory");
     }
@@ -545,16 +455,11 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     KP_HIP(hipMemsetAsync(d_hist, 0, cnts * 8, st));
     KP_HIP(hipMemsetAsync(d_other, 0, n_regions * 16, st));
     if (!items.empty()) {
-        const size_t b_items = g_up(items.size() * sizeof(kp_p_item));
         uint8_t *d_seq = nullptr;
-        if ((rc = pred_upload_contig(c, "kp_pred_regions", seq, n, b_items, &d_seq))) return rc;
-        kp_p_item *d_items = (kp_p_item *)c->seq_in.take(b_items);
-        if ((rc = c->seq_in.check("kp_pred_regions"))) return rc;
-        KP_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(kp_p_item), hipMemcpyHostToDevice, st));
+        kp_p_item *d_items = nullptr;
+        if ((rc = scan_upload(c, "kp_pred_regions", seq, n, items, 0, &d_seq, &d_items))) return rc;
         const size_t lds_bytes = lds ? (size_t)P * 4 : 0;
-        // a persistent grid: as many workgroups as are resident at once
-        const int per_cu = lds_bytes <= 16u * 1024u ? 8 : (lds_bytes <= 40u * 1024u ? 4 : 2);
-        const uint64_t grid = pred_grid(c, items.size(), per_cu);
+        const uint64_t grid = scan_grid(c, items.size(), scan_per_cu(lds_bytes), "KP_PRED_GRID");
         kp_p_args A;
         A.seq = d_seq;
         A.items = d_items;
@@ -567,13 +472,12 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
         A.lut = s->d_lut;
         A.hist = d_hist;
         A.other = d_other;
-        KP_HIP(hipEventRecord(c->ev[0], st));
+        if ((rc = scan_mark(c, 0))) return rc;
         if (lds)
             hipLaunchKernelGGL((kp_pred_scan_kernel<true>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
         else
             hipLaunchKernelGGL((kp_pred_scan_kernel<false>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
+        if ((rc = scan_launched(c, 1))) return rc;
     }
     if (rates) {
         KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
@@ -587,7 +491,7 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     KP_HIP(hipStreamSynchronize(st));
     if (!items.empty()) {
         float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
         s->st.scan_ms += ms;
         s->st.path = lds ? 1u : 2u;
     }
@@ -603,7 +507,7 @@ int kp_pred_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
 
 int kp_pred_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uint64_t end, int32_t *pid) {
     kp_pred_sess *s = pred_sess(c);
-    int rc = pred_check_contig("kp_pred_track", s, seq, n);
+    int rc = scan_check_contig("kp_pred_track", s->active, seq, n, "kp_pred_begin");
     if (rc) return rc;
     if (begin > end || end > n) return fail(KP_E_ARG, "kp_pred_track: begin > end or a range outside the contig");
     const uint64_t len = end - begin;
@@ -611,7 +515,7 @@ int kp_pred_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     if (!pid) return fail(KP_E_ARG, "kp_pred_track: null output");
     const int k = s->k;
     const uint32_t mask = (uint32_t)(s->cells - 1);
-    const uint64_t n_items = (len + KP_S_TILE - 1) / KP_S_TILE;
+    const uint64_t n_items = scan_tiles(len);
     if (!c) {
         for (uint64_t i = 0; i < len; ++i) {
             uint32_t code = 0;
@@ -625,16 +529,17 @@ int kp_pred_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     int32_t *d_pid = (int32_t *)c->arena.take(len * 4);
     if ((rc = c->arena.check("kp_pred_track"))) return rc;
     uint8_t *d_seq = nullptr;
-    if ((rc = pred_upload_contig(c, "kp_pred_track", seq, n, 0, &d_seq))) return rc;
-    if ((rc = c->seq_in.check("kp_pred_track"))) return rc;
+    if ((rc = scan_upload(c, "kp_pred_track", seq, n, {}, 0, &d_seq, nullptr))) return rc;
     hipStream_t st = c->stream;
-    const uint64_t grid = pred_grid(c, n_items, 4);  // 33 KB of LDS per workgroup
+    const uint64_t grid = scan_grid(c, n_items, 4, "KP_PRED_GRID");  // 33 KB of LDS per workgroup
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     kp_p_targs A;
     A.seq = d_seq;
     A.begin = (uint32_t)begin;
     A.len = (uint32_t)len;
-    A.lo = (uint32_t)(k / 2);
-    A.hi = n >= (uint64_t)k ? (uint32_t)(n - (uint64_t)k + A.lo + 1) : A.lo;
+    A.lo = (uint32_t)lo;
+    A.hi = (uint32_t)hi;
     A.n_items = (uint32_t)n_items;
     A.steps = (uint32_t)((n_items + grid - 1) / grid);
     A.k = k;
@@ -642,14 +547,13 @@ int kp_pred_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     A.mask = mask;
     A.lut = s->d_lut;
     A.pid = d_pid;
-    KP_HIP(hipEventRecord(c->ev[0], st));
+    if ((rc = scan_mark(c, 0))) return rc;
     hipLaunchKernelGGL(kp_pred_track_kernel, dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-    KP_HIP(hipGetLastError());
-    KP_HIP(hipEventRecord(c->ev[1], st));
+    if ((rc = scan_launched(c, 1))) return rc;
     KP_HIP(hipMemcpyAsync(pid, d_pid, len * 4, hipMemcpyDeviceToHost, st));
     KP_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
     s->st.scan_ms += ms;
     s->st.items += n_items;
     return KP_OK;
@@ -657,7 +561,7 @@ int kp_pred_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
 
 int kp_pred_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos, uint64_t n_sites, int32_t *pid) {
     kp_pred_sess *s = pred_sess(c);
-    int rc = pred_check_contig("kp_pred_sites", s, seq, n);
+    int rc = scan_check_contig("kp_pred_sites", s->active, seq, n, "kp_pred_begin");
     if (rc) return rc;
     if (n_sites && (!pos || !pid)) return fail(KP_E_ARG, "kp_pred_sites: null positions or output");
     if (n_sites >= (1ull << 39)) return fail(KP_E_ARG, "kp_pred_sites: 2^39 sites or more in one call");
@@ -680,7 +584,7 @@ int kp_pred_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos
     int32_t *d_pid = (int32_t *)c->arena.take(n_sites * 4);
     if ((rc = c->arena.check("kp_pred_sites"))) return rc;
     uint8_t *d_seq = nullptr;
-    if ((rc = pred_upload_contig(c, "kp_pred_sites", seq, n, g_up(n_sites * 8), &d_seq))) return rc;
+    if ((rc = scan_upload(c, "kp_pred_sites", seq, n, {}, g_up(n_sites * 8), &d_seq, nullptr))) return rc;
     uint64_t *d_pos = (uint64_t *)c->seq_in.take(n_sites * 8);
     if ((rc = c->seq_in.check("kp_pred_sites"))) return rc;
     hipStream_t st = c->stream;

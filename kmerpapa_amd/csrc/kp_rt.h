@@ -176,6 +176,23 @@ struct kp_ctx {
     kp_spec_sess spec;
 };
 
+// What every genome scan session checks of a contig (kp_seq.h, kp_pred.h, kp_spec.h and the calls of
+// a kp_spec session).  `begin_name` opens the session whose `active` this is
+static int scan_check_contig(const std::string &w, bool active, const uint8_t *seq, uint64_t n, const char *begin_name) {
+    if (!active) return fail(KP_E_STATE, w + ": no session (" + begin_name + " first)");
+    if (n && !seq) return fail(KP_E_ARG, w + ": null sequence");
+    if (n >= (1ull << 32)) return fail(KP_E_ARG, w + ": a contig of 2^32 bases or more");
+    return KP_OK;
+}
+
+// a persistent grid: as many workgroups as are resident at once, at most the units and the knob
+static uint64_t scan_grid(kp_ctx *c, uint64_t n_units, int per_cu, const char *knob) {
+    uint64_t grid = std::min<uint64_t>(n_units, (uint64_t)c->cus * per_cu);
+    const long grid_env = env_int(knob, 0);
+    if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
+    return grid;
+}
+
 extern "C" {
 
 const char *kp_last_error(void) { return g_err.c_str(); }

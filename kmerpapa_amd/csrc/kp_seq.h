@@ -210,13 +210,6 @@ static std::vector<kp_s_item> seq_items(uint64_t n, int k, const uint64_t *rb, c
     return items;
 }
 
-static int seq_check_contig(const std::string &w, const kp_seq_sess *s, const uint8_t *seq, uint64_t n) {
-    if (!s->active) return fail(KP_E_STATE, w + ": no session (kp_seq_begin first)");
-    if (n && !seq) return fail(KP_E_ARG, w + ": null sequence");
-    if (n >= (1ull << 32)) return fail(KP_E_ARG, w + ": a contig of 2^32 bases or more");
-    return KP_OK;
-}
-
 // kp_seq_begin (pcols = 1) and kp_seq_begin_typed (pcols = 3)
 static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols) {
     kp_seq_sess *s = seq_sess(c);
@@ -293,7 +286,7 @@ int kp_seq_begin_typed(kp_ctx *c, int k, int fold) { return seq_begin("kp_seq_be
 int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
                 uint64_t n_regions) {
     kp_seq_sess *s = seq_sess(c);
-    int rc = seq_check_contig("kp_seq_scan", s, seq, n);
+    int rc = scan_check_contig("kp_seq_scan", s->active, seq, n, "kp_seq_begin");
     if (rc) return rc;
     if (n_regions && (!reg_begin || !reg_end)) return fail(KP_E_ARG, "kp_seq_scan: null regions");
     for (uint64_t r = 0; r < n_regions; ++r)
@@ -326,9 +319,7 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
         const size_t lds_bytes = lds ? (size_t)s->cells * 4 : 0;
         // a persistent grid: as many workgroups as are resident at once
         const int per_cu = !lds ? 8 : (lds_bytes <= 16u * 1024u ? 8 : (lds_bytes <= 40u * 1024u ? 4 : 2));
-        uint64_t grid = std::min<uint64_t>(items.size(), (uint64_t)c->cus * per_cu);
-        const long grid_env = env_int("KP_SEQ_GRID", 0);
-        if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
+        const uint64_t grid = scan_grid(c, items.size(), per_cu, "KP_SEQ_GRID");
         const uint64_t steps = (items.size() + grid - 1) / grid;
 
         const size_t b_seq = g_up(n + KP_S_PAD), b_items = g_up(items.size() * sizeof(kp_s_item));
@@ -375,7 +366,7 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
 
 int kp_seq_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos, uint64_t n_sites) {
     kp_seq_sess *s = seq_sess(c);
-    int rc = seq_check_contig("kp_seq_sites", s, seq, n);
+    int rc = scan_check_contig("kp_seq_sites", s->active, seq, n, "kp_seq_begin");
     if (rc) return rc;
     if (s->pcols != 1) return fail(KP_E_STATE, "kp_seq_sites: the session is typed (kp_seq_sites_typed)");
     if (n_sites && !pos) return fail(KP_E_ARG, "kp_seq_sites: null positions");

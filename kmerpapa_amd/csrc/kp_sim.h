@@ -142,7 +142,7 @@ __device__ inline uint32_t kp_sim_roll(const kp_sm_args &A, const kp_p_item it, 
         int4 p[KP_P_BATCH];
         double c[KP_P_BATCH][3];
 #pragma unroll
-        for (uint32_t q = 0; q < KP_P_BATCH; ++q) {
+        for (uint32_t q = 0; q < KP_P_BATCH; ++q) {  // (kp_scan_batch with the REF as read kept beside the code)
             const uint32_t j = jb + q;
             if (j >= off && j < end) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), A.mask, top);
             has[q] = j >= full0 && j < end && w.valid >= (uint32_t)k;
@@ -296,13 +296,6 @@ static int sim_check_rates(const kp_spec_sess *s, const double *rates, double sc
     return KP_OK;
 }
 
-static uint64_t sim_grid(kp_ctx *c, uint64_t n_items, int per_cu) {
-    uint64_t grid = std::min<uint64_t>(n_items, (uint64_t)c->cus * per_cu);
-    const long grid_env = env_int("KP_SIM_GRID", 0);
-    if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
-    return grid;
-}
-
 extern "C" {
 
 int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_id, const uint64_t *reg_begin,
@@ -310,7 +303,7 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
                      uint32_t replicate, uint64_t cap, uint64_t *out_pos, uint8_t *out_alt, int32_t *out_pid,
                      uint64_t *n_hits) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_simulate", s, seq, n);
+    int rc = scan_check_contig("kp_spec_simulate", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (!n_hits) return fail(KP_E_ARG, "kp_spec_simulate: null n_hits");
     if (!rates) return fail(KP_E_ARG, "kp_spec_simulate: null rates");
@@ -318,20 +311,14 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
     if (n_regions && (!reg_begin || !reg_end)) return fail(KP_E_ARG, "kp_spec_simulate: null regions");
     if (cap && (!out_pos || !out_alt || !out_pid)) return fail(KP_E_ARG, "kp_spec_simulate: null outputs with cap > 0");
     if ((rc = sim_check_rates(s, rates, scale))) return rc;
-    for (uint64_t r = 0; r < n_regions; ++r) {
-        if (reg_begin[r] > reg_end[r] || reg_end[r] > n)
-            return fail(KP_E_ARG, "kp_spec_simulate: region " + std::to_string(r) + " has begin > end or lies outside the contig");
-        if (r && reg_begin[r] < reg_end[r - 1])
-            return fail(KP_E_ARG, "kp_spec_simulate: region " + std::to_string(r) + " begins before region " +
-                                      std::to_string(r - 1) + " ends (regions must be ascending and disjoint)");
-    }
+    if ((rc = scan_check_regions("kp_spec_simulate", n, reg_begin, reg_end, n_regions, true))) return rc;
     s->sim = kp_spec_sim_stats{};
     *n_hits = 0;
     const int k = s->k;
     const uint32_t P = (uint32_t)s->pats.size();
     const uint32_t mask = (uint32_t)(s->cells - 1);
-    // centres whose window lies inside the contig: [lo, hi)
-    const uint64_t lo = (uint64_t)(k / 2), hi = n >= (uint64_t)k ? n - (uint64_t)k + lo + 1 : lo;
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     if (!c) {
         std::vector<uint64_t> h_pos;
         std::vector<uint8_t> h_alt;
@@ -340,7 +327,7 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
         try {
             for (uint64_t r = 0; r < n_regions; ++r) {
                 const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-                if (e > b) n_items += (e - b + KP_S_TILE - 1) / KP_S_TILE;
+                n_items += scan_pieces(reg_begin[r], reg_end[r], lo, hi);
                 for (uint64_t p = b; p < e; ++p) {
                     uint32_t code = 0;
                     if (!kp_p_window(seq, n, p, k, s->fold, mask, &code)) continue;
@@ -378,13 +365,7 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
     std::vector<kp_p_item> items;
     uint64_t centres = 0;
     try {
-        for (uint64_t r = 0; r < n_regions; ++r) {
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            for (uint64_t f = b; f < e; f += KP_S_TILE) {
-                items.push_back(kp_p_item{(uint32_t)f, (uint32_t)std::min<uint64_t>(KP_S_TILE, e - f), (uint32_t)r});
-                centres += items.back().count;
-            }
-        }
+        for (uint64_t r = 0; r < n_regions; ++r) centres += scan_cut(items, reg_begin[r], reg_end[r], lo, hi, (uint32_t)r);
     } catch (const std::bad_alloc &) {
         return fail(KP_E_NOMEM, "kp_spec_simulate: the work items do not fit host memory");
     }
@@ -405,12 +386,9 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
     int32_t *d_pid = (int32_t *)c->arena.take(room * 4);
     if ((rc = c->arena.check("kp_spec_simulate"))) return rc;
     hipStream_t st = c->stream;
-    const size_t b_items = g_up(n_items * sizeof(kp_p_item));
     uint8_t *d_seq = nullptr;
-    if ((rc = pred_upload_contig(c, "kp_spec_simulate", seq, n, b_items, &d_seq))) return rc;
-    kp_p_item *d_items = (kp_p_item *)c->seq_in.take(b_items);
-    if ((rc = c->seq_in.check("kp_spec_simulate"))) return rc;
-    KP_HIP(hipMemcpyAsync(d_items, items.data(), n_items * sizeof(kp_p_item), hipMemcpyHostToDevice, st));
+    kp_p_item *d_items = nullptr;
+    if ((rc = scan_upload(c, "kp_spec_simulate", seq, n, items, 0, &d_seq, &d_items))) return rc;
     KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
     KP_HIP(hipMemsetAsync(d_total, 0, 8, st));
     KP_HIP(hipMemsetAsync(d_windows, 0, 8, st));
@@ -435,21 +413,20 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
     A.out_pid = d_pid;
     A.n_out = 0;
     // persistent grids: as many workgroups as are resident at once
-    uint64_t grid = sim_grid(c, n_items, 4);
+    uint64_t grid = scan_grid(c, n_items, 4, "KP_SIM_GRID");
     A.steps = (uint32_t)((n_items + grid - 1) / grid);
-    KP_HIP(hipEventRecord(c->ev[0], st));
+    if ((rc = scan_mark(c, 0))) return rc;
     hipLaunchKernelGGL(kp_sim_count_kernel, dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
     KP_HIP(hipGetLastError());
     hipLaunchKernelGGL(kp_sim_offsets_kernel, dim3(1), dim3(KP_SM_SCAN), 0, st, d_hits, (uint32_t)n_items, d_off, d_total);
-    KP_HIP(hipGetLastError());
-    KP_HIP(hipEventRecord(c->ev[1], st));
+    if ((rc = scan_launched(c, 1))) return rc;
     uint32_t total = 0;
     unsigned long long windows = 0;
     KP_HIP(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
     KP_HIP(hipMemcpyAsync(&windows, d_windows, 8, hipMemcpyDeviceToHost, st));
     KP_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
     s->sim.count_ms = ms;
     s->sim.windows = windows;
     s->sim.hits = total;
@@ -457,17 +434,16 @@ int kp_spec_simulate(kp_ctx *c, const uint8_t *seq, uint64_t n, uint32_t contig_
     if (total == 0 || total > cap) return KP_OK;
     if (total > room) return fail(KP_E_PARITY, "kp_spec_simulate: more hits than centres");
     A.n_out = total;
-    grid = sim_grid(c, n_items, 3);  // 41 KB of LDS per workgroup
+    grid = scan_grid(c, n_items, 3, "KP_SIM_GRID");  // 41 KB of LDS per workgroup
     A.steps = (uint32_t)((n_items + grid - 1) / grid);
-    KP_HIP(hipEventRecord(c->ev[2], st));
+    if ((rc = scan_mark(c, 2))) return rc;
     hipLaunchKernelGGL(kp_sim_write_kernel, dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-    KP_HIP(hipGetLastError());
-    KP_HIP(hipEventRecord(c->ev[3], st));
+    if ((rc = scan_launched(c, 3))) return rc;
     KP_HIP(hipMemcpyAsync(out_pos, d_pos, (size_t)total * 8, hipMemcpyDeviceToHost, st));
     KP_HIP(hipMemcpyAsync(out_alt, d_alt, (size_t)total, hipMemcpyDeviceToHost, st));
     KP_HIP(hipMemcpyAsync(out_pid, d_pid, (size_t)total * 4, hipMemcpyDeviceToHost, st));
     KP_HIP(hipStreamSynchronize(st));
-    KP_HIP(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    if ((rc = scan_elapsed(c, 2, 3, &ms))) return rc;
     s->sim.write_ms = ms;
     return KP_OK;
 }

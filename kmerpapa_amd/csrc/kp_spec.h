@@ -6,9 +6,10 @@
 // every type.  One pattern list holds every type's partition (ptype[p] = the type of pattern p),
 // and one table of 16-byte entries {pattern of slot 0, 1, 2, -1} per code answers all three with
 // one gather.  Windows, validity, the centre and folding are kp_seq.h's (kp_s_class / kp_s_step /
-// kp_s_code), matching is kp_apply.h's (kp_a_onehot / kp_a_match), the window of a site and the
-// aligned loads are kp_pred.h's (kp_p_window / kp_p_load).  Counts are integers and `expected` is
-// a float64 sum in pattern order per type, so a device session equals the host session bit for bit.
+// kp_s_code), matching is kp_apply.h's (kp_a_onehot / kp_a_match), the window of a site is
+// kp_pred.h's (kp_p_window), the scan's skeleton on device and host is kp_scan.h's.  Counts are
+// integers and `expected` is a float64 sum in pattern order per type, so a device session equals
+// the host session bit for bit.
 //
 //   kp_spec_lut_kernel        one k-mer code per thread against every pattern, staged through LDS
 //                             in tiles with their slots (as kp_pred_lut_kernel): the first match
@@ -158,15 +159,7 @@ __global__ void __launch_bounds__(KP_S_THREADS) kp_spec_scan_kernel(kp_sp_args A
             uint32_t code[KP_P_BATCH];
             bool has[KP_P_BATCH];
             int4 p[KP_P_BATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < KP_P_BATCH; ++q) {
-                const uint32_t j = jb + q;
-                if (j >= off && j < end) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), A.mask, top);
-                const bool full = j >= full0 && j < end;
-                has[q] = full && w.valid >= (uint32_t)k;
-                inv += full && !has[q];
-                code[q] = kp_s_code(w, k, A.fold);
-            }
+            kp_scan_batch(w, d, jb, off, end, full0, k, A.fold, A.mask, top, code, has, inv);
 #pragma unroll
             for (uint32_t q = 0; q < KP_P_BATCH; ++q)  // (code <= mask: the entry lies inside the table)
                 p[q] = has[q] ? A.lut[code[q]] : make_int4(KP_P_INVALID, KP_P_INVALID, KP_P_INVALID, KP_P_INVALID);
@@ -235,19 +228,14 @@ __global__ void __launch_bounds__(KP_S_THREADS) kp_spec_track_kernel(kp_sp_targs
         for (int plane = 0; plane < 3; ++plane) {
 #pragma unroll
             for (uint32_t q = 0; q < KP_S_RUN; ++q) buf[q * KP_P_ROW + tid] = KP_P_INVALID;
+            uint32_t inv = 0;  // (not reported: the slots of invalid windows keep their -2)
             kp_s_win w{0u, 0u, 0u};
 #pragma unroll
             for (uint32_t jb = 0; jb < 64; jb += KP_P_BATCH) {
                 uint32_t code[KP_P_BATCH];
                 bool has[KP_P_BATCH];
                 int4 p[KP_P_BATCH];
-#pragma unroll
-                for (uint32_t q = 0; q < KP_P_BATCH; ++q) {
-                    const uint32_t j = jb + q;
-                    if (j >= off && j < end) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), A.mask, top);
-                    has[q] = j >= full0 && j < end && w.valid >= (uint32_t)k;
-                    code[q] = kp_s_code(w, k, A.fold);
-                }
+                kp_scan_batch(w, d, jb, off, end, full0, k, A.fold, A.mask, top, code, has, inv);
 #pragma unroll
                 for (uint32_t q = 0; q < KP_P_BATCH; ++q) p[q] = has[q] ? A.lut[code[q]] : make_int4(0, 0, 0, 0);
 #pragma unroll
@@ -340,13 +328,6 @@ static thread_local kp_spec_sess g_spec_host;
 
 static kp_spec_sess *spec_sess(kp_ctx *c) { return c ? &c->spec : &g_spec_host; }
 
-static int spec_check_contig(const std::string &w, const kp_spec_sess *s, const uint8_t *seq, uint64_t n) {
-    if (!s->active) return fail(KP_E_STATE, w + ": no session (kp_spec_begin first)");
-    if (n && !seq) return fail(KP_E_ARG, w + ": null sequence");
-    if (n >= (1ull << 32)) return fail(KP_E_ARG, w + ": a contig of 2^32 bases or more");
-    return KP_OK;
-}
-
 // positions on the contig and ALT bytes that are bases
 static int spec_check_sites(const std::string &w, uint64_t n, const uint64_t *pos, const uint8_t *alt, uint64_t n_sites) {
     if (n_sites && (!pos || !alt)) return fail(KP_E_ARG, w + ": null positions or ALT bases");
@@ -362,52 +343,22 @@ static int spec_check_sites(const std::string &w, uint64_t n, const uint64_t *po
     return KP_OK;
 }
 
-// kp_pred's pred_arena for the 16-byte table: the table first, then `extra` bytes the caller takes
+// scan_arena for the table of 16-byte entries: the table first, then `extra` bytes the caller takes
 static int spec_arena(kp_ctx *c, const char *who, size_t extra) {
     kp_spec_sess *s = &c->spec;
     const uint32_t P = (uint32_t)s->pats.size();
-    const size_t b_lut = g_up((size_t)s->cells * 16), b_pats = g_up((size_t)P * 8) + g_up((size_t)P * 4);
-    const size_t need = b_lut + std::max(extra, b_pats);
-    if (need > c->arena.bytes) {
-        size_t fr = 0, tot = 0;
-        KP_HIP(hipMemGetInfo(&fr, &tot));
-        if (need + (2ull << 30) > fr + c->arena.bytes)
-            return fail(KP_E_NOMEM, std::string(who) + ": the spectrum table of " + std::to_string(s->k) +
-                                        "-mers and this call's buffers need " + std::to_string(need >> 20) +
-                                        " MiB of device memory, " + std::to_string((fr + c->arena.bytes) >> 20) +
-                                        " MiB are free (2 GiB stay free)");
-        s->lut_ok = false;
-    }
-    int rc = c->arena.reserve(who, need);
-    if (rc) return rc;
-    s->d_lut = (int32_t *)c->arena.take((size_t)s->cells * 16);
-    if (!s->lut_ok) {
+    return scan_arena(c, s, who, "spectrum", 16, g_up((size_t)P * 8) + g_up((size_t)P * 4), extra, [&]() -> int {
         uint64_t *d_pats = (uint64_t *)c->arena.take((size_t)P * 8);
         uint32_t *d_type = (uint32_t *)c->arena.take((size_t)P * 4);
-        if ((rc = c->arena.check(who))) return rc;
-        hipStream_t st = c->stream;
-        KP_HIP(hipMemcpyAsync(d_pats, s->pats.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
-        KP_HIP(hipMemcpyAsync(d_type, s->ptype.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-        KP_HIP(hipEventRecord(c->ev[0], st));
-        hipLaunchKernelGGL(kp_spec_lut_kernel, dim3((unsigned)((s->cells + 255) / 256)), dim3(256), 0, st, d_pats, d_type, P,
-                           s->k, s->fold, (uint32_t)s->cells, (int4 *)s->d_lut);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
-        KP_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        s->st.lut_ms = ms;
-        s->lut_ok = true;
-        c->arena.used = b_lut;  // the staged patterns are done with
-    }
-    return KP_OK;
-}
-
-static uint64_t spec_grid(kp_ctx *c, uint64_t n_items, int per_cu) {
-    uint64_t grid = std::min<uint64_t>(n_items, (uint64_t)c->cus * per_cu);
-    const long grid_env = env_int("KP_SPEC_GRID", 0);
-    if (grid_env > 0) grid = std::min<uint64_t>(grid, (uint64_t)grid_env);
-    return grid;
+        int rc = c->arena.check(who);
+        if (rc) return rc;
+        KP_HIP(hipMemcpyAsync(d_pats, s->pats.data(), (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+        KP_HIP(hipMemcpyAsync(d_type, s->ptype.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = scan_mark(c, 0))) return rc;
+        hipLaunchKernelGGL(kp_spec_lut_kernel, dim3((unsigned)((s->cells + 255) / 256)), dim3(256), 0, c->stream, d_pats,
+                           d_type, P, s->k, s->fold, (uint32_t)s->cells, (int4 *)s->d_lut);
+        return scan_launched(c, 1);
+    });
 }
 
 extern "C" {
@@ -488,20 +439,18 @@ int kp_spec_begin(kp_ctx *c, int k, int fold, const uint64_t *patterns, const ui
 int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
                     uint64_t n_regions, const double *rates, uint64_t *hist, uint64_t *other, double *expected) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_regions", s, seq, n);
+    int rc = scan_check_contig("kp_spec_regions", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (n_regions >= (1ull << 32)) return fail(KP_E_ARG, "kp_spec_regions: 2^32 regions or more in one call");
     if (n_regions && (!reg_begin || !reg_end || !other)) return fail(KP_E_ARG, "kp_spec_regions: null regions or counters");
     if (rates && n_regions && !expected) return fail(KP_E_ARG, "kp_spec_regions: rates without a place for the sums");
-    for (uint64_t r = 0; r < n_regions; ++r)
-        if (reg_begin[r] > reg_end[r] || reg_end[r] > n)
-            return fail(KP_E_ARG, "kp_spec_regions: region " + std::to_string(r) + " has begin > end or lies outside the contig");
+    if ((rc = scan_check_regions("kp_spec_regions", n, reg_begin, reg_end, n_regions, false))) return rc;
     if (!n_regions) return KP_OK;
     const int k = s->k;
     const uint32_t P = (uint32_t)s->pats.size();
     const uint32_t mask = (uint32_t)(s->cells - 1);
-    // centres whose window lies inside the contig: [lo, hi)
-    const uint64_t lo = (uint64_t)(k / 2), hi = n >= (uint64_t)k ? n - (uint64_t)k + lo + 1 : lo;
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     if (!c) {
         std::vector<uint64_t> row;
         try {
@@ -527,8 +476,7 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
                         ++none[e];
                 }
             }
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            if (e > b) n_items += (e - b + KP_S_TILE - 1) / KP_S_TILE;
+            n_items += scan_pieces(reg_begin[r], reg_end[r], lo, hi);
             for (int e3 = 0; e3 < 3; ++e3) other[4 * r + e3] = none[e3];
             other[4 * r + 3] = inv;
             s->st.unmatched += none[0] + none[1] + none[2];
@@ -557,12 +505,8 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     std::vector<uint64_t> off_contig;  // per region: centres outside [lo, hi)
     try {
         off_contig.resize(n_regions);
-        for (uint64_t r = 0; r < n_regions; ++r) {
-            const uint64_t b = std::max(reg_begin[r], lo), e = std::min(reg_end[r], hi);
-            off_contig[r] = reg_end[r] - reg_begin[r] - (e > b ? e - b : 0);
-            for (uint64_t f = b; f < e; f += KP_S_TILE)
-                items.push_back(kp_p_item{(uint32_t)f, (uint32_t)std::min<uint64_t>(KP_S_TILE, e - f), (uint32_t)r});
-        }
+        for (uint64_t r = 0; r < n_regions; ++r)
+            off_contig[r] = reg_end[r] - reg_begin[r] - scan_cut(items, reg_begin[r], reg_end[r], lo, hi, (uint32_t)r);
     } catch (const std::bad_alloc &) {
         return fail(KP_E_NOMEM, "kp_spec_regions: the work items do not fit host memory");
     }
@@ -582,16 +526,11 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     KP_HIP(hipMemsetAsync(d_hist, 0, cnts * 8, st));
     KP_HIP(hipMemsetAsync(d_other, 0, n_regions * 32, st));
     if (!items.empty()) {
-        const size_t b_items = g_up(items.size() * sizeof(kp_p_item));
         uint8_t *d_seq = nullptr;
-        if ((rc = pred_upload_contig(c, "kp_spec_regions", seq, n, b_items, &d_seq))) return rc;
-        kp_p_item *d_items = (kp_p_item *)c->seq_in.take(b_items);
-        if ((rc = c->seq_in.check("kp_spec_regions"))) return rc;
-        KP_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(kp_p_item), hipMemcpyHostToDevice, st));
+        kp_p_item *d_items = nullptr;
+        if ((rc = scan_upload(c, "kp_spec_regions", seq, n, items, 0, &d_seq, &d_items))) return rc;
         const size_t lds_bytes = lds ? (size_t)P * 4 : 0;
-        // a persistent grid: as many workgroups as are resident at once
-        const int per_cu = lds_bytes <= 16u * 1024u ? 8 : (lds_bytes <= 40u * 1024u ? 4 : 2);
-        const uint64_t grid = spec_grid(c, items.size(), per_cu);
+        const uint64_t grid = scan_grid(c, items.size(), scan_per_cu(lds_bytes), "KP_SPEC_GRID");
         kp_sp_args A;
         A.seq = d_seq;
         A.items = d_items;
@@ -604,13 +543,12 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
         A.lut = (const int4 *)s->d_lut;
         A.hist = d_hist;
         A.other = d_other;
-        KP_HIP(hipEventRecord(c->ev[0], st));
+        if ((rc = scan_mark(c, 0))) return rc;
         if (lds)
             hipLaunchKernelGGL((kp_spec_scan_kernel<true>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
         else
             hipLaunchKernelGGL((kp_spec_scan_kernel<false>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-        KP_HIP(hipGetLastError());
-        KP_HIP(hipEventRecord(c->ev[1], st));
+        if ((rc = scan_launched(c, 1))) return rc;
     }
     if (rates) {
         KP_HIP(hipMemcpyAsync(d_rates, rates, (size_t)P * 8, hipMemcpyHostToDevice, st));
@@ -627,7 +565,7 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
     KP_HIP(hipStreamSynchronize(st));
     if (!items.empty()) {
         float ms = 0.f;
-        KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
         s->st.scan_ms += ms;
         s->st.path = lds ? 1u : 2u;
     }
@@ -644,7 +582,7 @@ int kp_spec_regions(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *r
 
 int kp_spec_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uint64_t end, int32_t *pid) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_track", s, seq, n);
+    int rc = scan_check_contig("kp_spec_track", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if (begin > end || end > n) return fail(KP_E_ARG, "kp_spec_track: begin > end or a range outside the contig");
     const uint64_t len = end - begin;
@@ -652,7 +590,7 @@ int kp_spec_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     if (!pid) return fail(KP_E_ARG, "kp_spec_track: null output");
     const int k = s->k;
     const uint32_t mask = (uint32_t)(s->cells - 1);
-    const uint64_t n_items = (len + KP_S_TILE - 1) / KP_S_TILE;
+    const uint64_t n_items = scan_tiles(len);
     if (!c) {
         for (uint64_t i = 0; i < len; ++i) {
             uint32_t code = 0;
@@ -668,16 +606,17 @@ int kp_spec_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     int32_t *d_pid = (int32_t *)c->arena.take(3 * plane);
     if ((rc = c->arena.check("kp_spec_track"))) return rc;
     uint8_t *d_seq = nullptr;
-    if ((rc = pred_upload_contig(c, "kp_spec_track", seq, n, 0, &d_seq))) return rc;
-    if ((rc = c->seq_in.check("kp_spec_track"))) return rc;
+    if ((rc = scan_upload(c, "kp_spec_track", seq, n, {}, 0, &d_seq, nullptr))) return rc;
     hipStream_t st = c->stream;
-    const uint64_t grid = spec_grid(c, n_items, 4);  // 33 KB of LDS per workgroup
+    const uint64_t grid = scan_grid(c, n_items, 4, "KP_SPEC_GRID");  // 33 KB of LDS per workgroup
+    uint64_t lo = 0, hi = 0;
+    scan_centres(n, k, &lo, &hi);
     kp_sp_targs A;
     A.seq = d_seq;
     A.begin = (uint32_t)begin;
     A.len = (uint32_t)len;
-    A.lo = (uint32_t)(k / 2);
-    A.hi = n >= (uint64_t)k ? (uint32_t)(n - (uint64_t)k + A.lo + 1) : A.lo;
+    A.lo = (uint32_t)lo;
+    A.hi = (uint32_t)hi;
     A.n_items = (uint32_t)n_items;
     A.steps = (uint32_t)((n_items + grid - 1) / grid);
     A.k = k;
@@ -686,15 +625,14 @@ int kp_spec_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
     A.lut = (const int4 *)s->d_lut;
     A.pid = d_pid;
     A.plane = plane / 4;
-    KP_HIP(hipEventRecord(c->ev[0], st));
+    if ((rc = scan_mark(c, 0))) return rc;
     hipLaunchKernelGGL(kp_spec_track_kernel, dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
-    KP_HIP(hipGetLastError());
-    KP_HIP(hipEventRecord(c->ev[1], st));
+    if ((rc = scan_launched(c, 1))) return rc;
     for (int e = 0; e < 3; ++e)
         KP_HIP(hipMemcpyAsync(pid + e * len, d_pid + e * (plane / 4), len * 4, hipMemcpyDeviceToHost, st));
     KP_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    KP_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if ((rc = scan_elapsed(c, 0, 1, &ms))) return rc;
     s->st.scan_ms += ms;
     s->st.items += n_items;
     return KP_OK;
@@ -703,7 +641,7 @@ int kp_spec_track(kp_ctx *c, const uint8_t *seq, uint64_t n, uint64_t begin, uin
 int kp_spec_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt, uint64_t n_sites,
                   int32_t *pid) {
     kp_spec_sess *s = spec_sess(c);
-    int rc = spec_check_contig("kp_spec_sites", s, seq, n);
+    int rc = scan_check_contig("kp_spec_sites", s->active, seq, n, "kp_spec_begin");
     if (rc) return rc;
     if ((rc = spec_check_sites("kp_spec_sites", n, pos, alt, n_sites))) return rc;
     if (!n_sites) return KP_OK;
@@ -723,7 +661,8 @@ int kp_spec_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos
     int32_t *d_pid = (int32_t *)c->arena.take(n_sites * 4);
     if ((rc = c->arena.check("kp_spec_sites"))) return rc;
     uint8_t *d_seq = nullptr;
-    if ((rc = pred_upload_contig(c, "kp_spec_sites", seq, n, g_up(n_sites * 8) + g_up(n_sites), &d_seq))) return rc;
+    if ((rc = scan_upload(c, "kp_spec_sites", seq, n, {}, g_up(n_sites * 8) + g_up(n_sites), &d_seq, nullptr)))
+        return rc;
     uint64_t *d_pos = (uint64_t *)c->seq_in.take(n_sites * 8);
     uint8_t *d_alt = (uint8_t *)c->seq_in.take(n_sites);
     if ((rc = c->seq_in.check("kp_spec_sites"))) return rc;
@@ -777,7 +716,7 @@ int kp_spec_host(int k, int fold, const uint64_t *patterns, const uint32_t *ptyp
 int kp_seq_sites_typed(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos, const uint8_t *alt,
                        uint64_t n_sites) {
     kp_seq_sess *s = seq_sess(c);
-    int rc = seq_check_contig("kp_seq_sites_typed", s, seq, n);
+    int rc = scan_check_contig("kp_seq_sites_typed", s->active, seq, n, "kp_seq_begin");
     if (rc) return rc;
     if (s->pcols != 3) return fail(KP_E_STATE, "kp_seq_sites_typed: the session is not typed (kp_seq_begin_typed)");
     if ((rc = spec_check_sites("kp_seq_sites_typed", n, pos, alt, n_sites))) return rc;

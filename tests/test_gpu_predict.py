@@ -237,6 +237,42 @@ def test_short_items_on_a_context_of_their_own(monkeypatch):
         own.close()
 
 
+def test_table_is_rebuilt_after_the_arena_grew(monkeypatch):
+    """On a context of its own the arena starts at the table plus its staged patterns (under 1 KiB
+    for k = 3).  The sites call fits in it, the 592 KB of counters of 2,000 regions do not: the arena
+    grows, which frees the table, and it is built again before the scan, the track and the second
+    sites call read it."""
+    _set(monkeypatch, {})
+    rng = np.random.RandomState(83)
+    n = 333
+    seq = R.random_seq(rng, n, lower=0.2)
+    seq[150] = ord("N")
+    begin = rng.randint(0, n - 5, size=2000)
+    regions = np.stack([begin, begin + rng.randint(1, 6, size=2000)], axis=1)
+    words, sw, rates, _ = _partition("NNN", 37)
+    sites = [0, 151, n - 1]
+
+    def calls(s):
+        s.pred_begin(3, words, sw, True)
+        try:
+            first = s.pred_sites(seq, sites)
+            hist, other, exp = s.pred_regions(seq, regions, rates, True)
+            track = s.pred_track(seq, 0, n)
+            return first, hist, other, exp, track, s.pred_sites(seq, sites)
+        finally:
+            s.pred_end()
+
+    ref = calls(engine.HostPred())
+    own = engine.Device(engine.visible_devices()[0])
+    try:
+        got = calls(own)
+    finally:
+        own.close()
+    for g, r in zip(got, ref):
+        assert g.dtype == r.dtype and g.shape == r.shape and g.tobytes() == r.tobytes()
+    assert ref[1].nbytes > 1 << 16 and int(ref[1].sum()) > 0 and (ref[4] == -2).sum() >= 5 and (ref[4] >= 0).any()
+
+
 def test_track(dev, tile, monkeypatch):
     _set(monkeypatch, {})
     rng = np.random.RandomState(61)

@@ -158,6 +158,46 @@ def test_contig_lengths_around_the_tile(dev, tile, monkeypatch, env, path):
         assert got[5]["lut_bytes"] == 16 * 4 ** k
 
 
+def test_table_is_rebuilt_after_the_arena_grew(monkeypatch):
+    """On a context of its own the arena starts at the table plus its staged patterns (under 2 KiB
+    for k = 3).  The sites call fits in it, the counters of 2,000 regions do not: the arena grows,
+    which frees the table, and it is built again before the scan, the null table, the track and
+    the second sites call read it."""
+    _set(monkeypatch, {})
+    rng = np.random.RandomState(89)
+    n = 333
+    seq = R.random_seq(rng, n, lower=0.2)
+    seq[150] = ord("N")
+    begin = rng.randint(0, n - 5, size=2000)
+    regions = np.stack([begin, begin + rng.randint(1, 6, size=2000)], axis=1)
+    words, ptype, rates, _ = _model(3, True, 6, 4)
+    draw = np.full(len(words), 0.05)  # (three types of a REF add up to 0.15 <= 1)
+    pos, alts = np.array([0, 151, n - 1]), np.frombuffer(b"CaT", np.uint8)
+
+    def calls(s):
+        s.spec_begin(3, words, ptype, True)
+        try:
+            first = s.spec_sites(seq, pos, alts)
+            hist, other, exp = s.spec_regions(seq, regions, rates, True)
+            null = s.spec_null(seq, regions[:50], draw, 7, 2, 1, 64)
+            track = s.spec_track(seq, 0, n)
+            return first, hist, other, exp, null, track, s.spec_sites(seq, pos, alts)
+        finally:
+            s.spec_end()
+
+    ref = calls(engine.HostSpec())
+    with _guard():
+        own = engine.Device(engine.visible_devices()[0])
+        try:
+            got = calls(own)
+        finally:
+            own.close()
+    for g, r in zip(got, ref):
+        assert g.dtype == r.dtype and g.shape == r.shape and g.tobytes() == r.tobytes()
+    assert ref[1].nbytes > 1 << 16 and int(ref[1].sum()) > 0 and int(ref[4].sum()) > 0
+    assert (ref[5] == -2).sum() >= 15 and (ref[5] >= 0).any()
+
+
 def test_k1_twelve_types_without_folding(dev, tile, monkeypatch):
     _set(monkeypatch, {})
     model = _model(1, False, 12, 1)

@@ -352,6 +352,76 @@ int kp_seq_host(int k, int fold, const uint8_t *seq, uint64_t n, int scan, const
                 const uint64_t *reg_end, uint64_t n_regions, const uint64_t *pos, uint64_t n_sites,
                 uint64_t *pos_counts, uint64_t *bg_counts, kp_seq_stats *stats);
 
+/* Breakpoint contexts of short insertions and deletions, and background counts of both strands.
+ * (No reference counterpart; the semantics are this project's own.)  Bases, validity and codes are
+ * kp_seq's above; two bytes are equal if they are the same base in either case, and an invalid
+ * byte equals nothing, not even itself.
+ * Breakpoint b, 0 <= b <= n, is the gap before position b.  Its window at even k = 2r is
+ * seq[b - r, b + r): kp_seq's window with centre b.  rc(w), the reverse complement of w, is the same
+ * breakpoint read on the other strand.
+ * A site is an insertion of a string I of L >= 1 bases at breakpoint b, or a deletion of
+ * [s, s + L), L >= 1, s + L <= n.  Its equivalence interval [lo, hi] is the contiguous range of
+ * placements that give the same mutated sequence:
+ *   insertion  a = the largest j with seq[b-1-t] == I[(L-1-t) mod L] for all t < j (t < b),
+ *              c = the largest j with seq[b+t] == I[t mod L] for all t < j (b + t < n);
+ *              lo = b - a, hi = b + c
+ *   deletion   with e = s + L: a = the largest j with seq[s-1-t] == seq[e-1-t] for all t < j
+ *              (t < s), c = the largest j with seq[s+t] == seq[e+t] for all t < j (e + t < n);
+ *              lo = s - a, hi = s + c
+ * The chosen breakpoint p: place 0 (left, the VCF convention) = lo, 1 (right) = hi, 2 (sample) =
+ * lo + (((uint64)x0 * (hi - lo + 1)) >> 32), x0 the first output word of Philox4x32-10 (the
+ * generator of kp_spec_simulate) keyed by the 64-bit seed on the counter (key low word, key high
+ * word, contig index, 0x494E444C); key is a uint64 the caller passes per site (kmerpapa-count: the
+ * 0-based line of the site in its file), so a recurrent indel draws independently and a draw
+ * depends on nothing but seed, contig and key.  The multiply-shift is not exactly uniform: the bias
+ * is below 2^-32 * span.
+ * An indel session has three positive columns of 4^k counters, ins, del_start and del_end, beside
+ * the background column.  An insertion adds 1 to ins at code(W(p)); a deletion adds 1 to del_start
+ * at code(W(p)) and 1 to del_end at code(W(p + L)).  A site any of whose windows runs off the
+ * contig or holds an invalid byte is skipped whole (a deletion counts in both columns or in
+ * neither) and counted in sites_skipped; it is placed first and checked after, never re-placed.
+ * With both != 0 every add at (column c, code w) comes with an add at (mirror(c), rc(w)), mirror
+ * swapping del_start and del_end and keeping ins, and kp_seq_scan adds 1 at code(w) and 1 at
+ * code(rc(w)) for every valid window (a palindromic window: 2 in one cell).  So ins and the
+ * background are rc-symmetric, del_end[w] == del_start[rc(w)], and the background sums to twice the
+ * stats' windows; del_start of such a session is the table to fit deletions on ("a deletion begins
+ * here, read 5' to 3'").  A site's windows, and all columns, depend only on its equivalence class
+ * and on place, never on the placement the caller passed.
+ *   kp_seq_begin_indel    k even, 2..14 (else KP_E_ARG); zeroes the four columns; the arena, its
+ *                         exclusions and KP_E_NOMEM as kp_seq_begin_typed.  kp_seq_scan works as
+ *                         in every session; kp_seq_sites and kp_seq_sites_typed are KP_E_STATE;
+ *                         kp_seq_end_typed reads out and ends it ([3][4^k] ins, del_start, del_end).
+ *   kp_seq_begin_strands  a plain session (k in 1..15, no folding, kp_seq_end) whose scan, with
+ *                         both != 0, adds on both strands: the background of an indel fit without
+ *                         the three positive columns.  kp_seq_sites in it is KP_E_STATE if both.
+ *   kp_seq_indels         one contig seq[n] with index `contig`, and per site pos[i] (b or s),
+ *                         del_len[i] (0 for an insertion) and key[i] (key NULL: i); insertion i is
+ *                         ins[ins_off[i] .. ins_off[i + 1]) (ins_off has n_sites + 1 entries,
+ *                         empty for a deletion).  resolved[n_sites][3] (may be NULL) receives lo, hi
+ *                         and p, for skipped sites too.  KP_E_ARG, before anything runs, names the
+ *                         first site with pos > n, a deletion past n, neither or both of
+ *                         del_len and inserted bytes, or a non-base byte in the insertion; fewer
+ *                         than 2^32 sites and inserted bytes per call.  KP_E_STATE outside an
+ *                         indel session.  The site arrays go into the allocation kp_seq_scan uses.
+ * With ctx = NULL the calls run this thread's host session, the serial definition with the same
+ * per-base functions; kp_seq_indel_host is one whole host session of one contig (pos_counts
+ * [3][4^k]).  On the device a wave searches one site's interval at a time, 64 positions per step
+ * and side (compare, ballot, first mismatch), at most n / 64 + 1 steps; then every lane places
+ * and counts its own site with global 64-bit atomics.  The both-strand scan is a separate build
+ * of the scan kernel; with LDS counters (k <= 7) a launch covers at most 2^17 items per
+ * workgroup, so that a uint32 counter taking 2 per centre cannot wrap (knob KP_SEQ_BOTH_STEPS,
+ * 1..131072, measurement and tests: every setting gives the same counts). */
+int kp_seq_begin_indel(kp_ctx *ctx, int k, int both);
+int kp_seq_begin_strands(kp_ctx *ctx, int k, int both);
+int kp_seq_indels(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig, const uint64_t *pos,
+                  const uint64_t *del_len, const uint64_t *key, const uint64_t *ins_off, const uint8_t *ins,
+                  uint64_t n_sites, int place, uint64_t seed, uint64_t *resolved);
+int kp_seq_indel_host(int k, int both, const uint8_t *seq, uint64_t n, uint32_t contig, int scan,
+                      const uint64_t *reg_begin, const uint64_t *reg_end, uint64_t n_regions, const uint64_t *pos,
+                      const uint64_t *del_len, const uint64_t *key, const uint64_t *ins_off, const uint8_t *ins,
+                      uint64_t n_sites, int place, uint64_t seed, uint64_t *pos_counts, uint64_t *bg_counts,
+                      uint64_t *resolved, kp_seq_stats *stats);
+
 /* A fitted partition taken back to the genome: per region, how many positions fall into each
  * pattern and how many mutations the rates expect there; per position or site, which pattern.
  * (No reference counterpart.)  Bases, windows, the centre and folding are kp_seq's above; pattern

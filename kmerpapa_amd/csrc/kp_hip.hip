@@ -34,7 +34,9 @@
 //                      totals, the pairwise overlap check and the table's -2 log-likelihood
 //   kp_seq_*         : k-mer context counts of a genome and its mutation sites (kp_seq.h): a
 //                      streaming scan with a rolling window per thread and a histogram in LDS
-//                      counters (k <= 7) or global 64-bit atomics; one thread per site
+//                      counters (k <= 7) or global 64-bit atomics; one thread per site; indels as
+//                      breakpoint contexts on both strands, each placed within its equivalence
+//                      interval, which a wave searches 64 positions per step (kp_indel.h)
 //   kp_pred_*        a fitted partition taken back to the genome (kp_pred.h): a lookup table from
 //                      k-mer code to pattern, the kp_seq roll in batches (kp_scan.h) with one gather per window, and
 //                      per-region pattern histograms in LDS counters or global 64-bit atomics
@@ -74,6 +76,8 @@
 //                  with the replicates on the lanes, and kp_spec_null
 //   kp_coding.h    the genetic code and per-pair class functions, the coding scan and sites kernels,
 //                  kp_spec_coding and kp_spec_coding_sites
+//   kp_indel.h     breakpoint contexts of indels: the equivalence interval of a site searched 64
+//                  positions per wave step, its placement and adds, kp_seq_indels
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -98,6 +102,7 @@
 #include "kp_pred.h"
 #include "kp_spec.h"
 #include "kp_sim.h"
+#include "kp_indel.h"
 #include "kp_null.h"
 #include "kp_coding.h"
 #include "kp_cnull.h"

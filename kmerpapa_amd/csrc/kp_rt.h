@@ -100,11 +100,14 @@ struct kp_arena {
 
 // One kp_seq_* session (kp_seq.h): the count columns live on the device (d_tab, in the
 // context's arena) or, for the host session, in h_tab.  A plain session has one positive column,
-// a typed one three (one per ALT slot, kp_spec.h).
+// a typed one three (one per ALT slot, kp_spec.h), and so has an indel session (ins, del_start,
+// del_end, kp_indel.h).
 struct kp_seq_sess {
     bool active = false;
     int k = 0, fold = 0;
-    int pcols = 1;         // positive columns: 1, or 3 in a typed session
+    int both = 0;          // every add comes with its mirror on the other strand (kp_seq_begin_strands / _indel)
+    bool indel = false;    // an indel session: kp_seq_indels fills the three positive columns
+    int pcols = 1;         // positive columns: 1, or 3 in a typed or an indel session
     uint64_t cells = 0;    // 4^k
     uint64_t centres = 0;  // centres of all work items so far (windows + windows_invalid)
     unsigned long long *d_tab = nullptr;   // [pcols + 1][cells]: positive, background

@@ -20,7 +20,9 @@
 //                        global 64-bit atomics straight into the table: at each step of the
 //                        roll the lanes that hold the same code as the wave's first emitting
 //                        lane add once, together (low-complexity runs, where a whole wave
-//                        holds one code), every other lane adds 1 on its own
+//                        holds one code), every other lane adds 1 on its own.  A session that counts
+//                        both strands (kp_seq_begin_strands, kp_seq_begin_indel) runs builds of
+//                        its own, <.., .., BOTH>, that emit the reverse complement's code as well
 //   kp_seq_sites_kernel  one thread per site: the k bytes around it, the same classify / fold
 //                        code, one global atomic per kept site
 //
@@ -42,6 +44,8 @@
 // that begin before the last byte of its last window (< n), so no load reaches n + 15; a thread
 // that owns none loads nothing
 #define KP_S_PAD 64
+// most items per workgroup and launch of a both-strand scan with LDS counters (kp_seq_scan_kernel)
+#define KP_S_BOTH_STEPS (1u << 17)
 
 __host__ __device__ inline uint32_t kp_s_class(uint32_t byte) {
     const uint32_t b = byte & 0xDFu;  // upper case
@@ -82,7 +86,13 @@ struct kp_s_args {
 
 #ifdef __HIPCC__
 
-template <bool LDS, bool MERGE>
+// BOTH (a session that counts both strands, kp_seq_begin_strands / kp_seq_begin_indel; no folding):
+// every window adds 1 at its forward code and 1 at its reverse complement's, a palindromic window
+// 2 to one cell.  A build of its own, so the one-strand builds carry no branch for it.  Its uint32
+// LDS counters take up to 2 per centre, so the host launches at most KP_S_BOTH_STEPS items per
+// workgroup at a time: a counter holds at most 2 * KP_S_BOTH_STEPS * KP_S_TILE = 2^31 at the
+// flush that ends a launch, whatever the contig and also with KP_SEQ_GRID=1.
+template <bool LDS, bool MERGE, bool BOTH = false>
 __global__ void __launch_bounds__(KP_S_THREADS) kp_seq_scan_kernel(kp_s_args A) {
     extern __shared__ uint32_t kp_s_cnt[];  // [cells] with LDS
     const uint32_t tid = threadIdx.x;
@@ -123,24 +133,27 @@ __global__ void __launch_bounds__(KP_S_THREADS) kp_seq_scan_kernel(kp_s_args A) 
             const bool act = j >= off && j < end;
             if (act) kp_s_step(w, kp_s_class((d[j >> 2] >> (8u * (j & 3u))) & 0xffu), mask, top);
             const bool has = act && w.valid >= (uint32_t)k;
-            const uint32_t code = kp_s_code(w, k, A.fold);
             mine += has;
-            if (LDS) {
-                if (has) atomicAdd(&kp_s_cnt[code], 1u);
-            } else if (MERGE) {
-                // the lanes that hold the first emitting lane's code add once, together
-                const unsigned long long m = __ballot(has);
-                if (m) {
-                    const int lead = __ffsll(m) - 1;
-                    const uint32_t c0 = (uint32_t)__shfl((int)code, lead, 64);
-                    const unsigned long long eq = __ballot(has && code == c0);
-                    if ((int)(tid & 63u) == lead)
-                        atomicAdd(&A.tab[c0], (unsigned long long)__popcll(eq));
-                    else if (has && code != c0)
-                        atomicAdd(&A.tab[code], 1ull);
+#pragma unroll
+            for (int strand = 0; strand < (BOTH ? 2 : 1); ++strand) {
+                const uint32_t code = BOTH ? (strand ? w.rc : w.fwd) : kp_s_code(w, k, A.fold);
+                if (LDS) {
+                    if (has) atomicAdd(&kp_s_cnt[code], 1u);
+                } else if (MERGE) {
+                    // the lanes that hold the first emitting lane's code add once, together
+                    const unsigned long long m = __ballot(has);
+                    if (m) {
+                        const int lead = __ffsll(m) - 1;
+                        const uint32_t c0 = (uint32_t)__shfl((int)code, lead, 64);
+                        const unsigned long long eq = __ballot(has && code == c0);
+                        if ((int)(tid & 63u) == lead)
+                            atomicAdd(&A.tab[c0], (unsigned long long)__popcll(eq));
+                        else if (has && code != c0)
+                            atomicAdd(&A.tab[code], 1ull);
+                    }
+                } else {
+                    if (has) atomicAdd(&A.tab[code], 1ull);
                 }
-            } else {
-                if (has) atomicAdd(&A.tab[code], 1ull);
             }
         }
     }
@@ -210,12 +223,15 @@ static std::vector<kp_s_item> seq_items(uint64_t n, int k, const uint64_t *rb, c
     return items;
 }
 
-// kp_seq_begin (pcols = 1) and kp_seq_begin_typed (pcols = 3)
-static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols) {
+// kp_seq_begin and kp_seq_begin_strands (pcols = 1), kp_seq_begin_typed (pcols = 3) and
+// kp_seq_begin_indel (pcols = 3, indel)
+static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols, int both = 0, bool indel = false) {
     kp_seq_sess *s = seq_sess(c);
     if (s->active) return fail(KP_E_STATE, w + ": a session is open (kp_seq_end first)");
     if (c && c->pred.active) return fail(KP_E_STATE, w + ": a kp_pred session holds the context's arena (kp_pred_end first)");
     if (c && c->spec.active) return fail(KP_E_STATE, w + ": a kp_spec session holds the context's arena (kp_spec_end first)");
+    if (indel && (k < 2 || k > 14 || k % 2))
+        return fail(KP_E_ARG, w + ": k must be even and 2..14 (the window of a breakpoint has k/2 bases on each side)");
     if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, w + ": k must be 1..15 (a dense table of 4^k counters)");
     if (fold && k % 2 == 0) return fail(KP_E_ARG, w + ": strand folding needs an odd k (a centre base)");
     const uint64_t cells = 1ull << (2 * k), cols = (uint64_t)pcols + 1;
@@ -247,6 +263,8 @@ static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols
     }
     s->k = k;
     s->fold = fold ? 1 : 0;
+    s->both = both ? 1 : 0;
+    s->indel = indel;
     s->pcols = pcols;
     s->cells = cells;
     s->centres = 0;
@@ -283,6 +301,10 @@ int kp_seq_begin(kp_ctx *c, int k, int fold) { return seq_begin("kp_seq_begin", 
 
 int kp_seq_begin_typed(kp_ctx *c, int k, int fold) { return seq_begin("kp_seq_begin_typed", c, k, fold, 3); }
 
+int kp_seq_begin_strands(kp_ctx *c, int k, int both) { return seq_begin("kp_seq_begin_strands", c, k, 0, 1, both); }
+
+int kp_seq_begin_indel(kp_ctx *c, int k, int both) { return seq_begin("kp_seq_begin_indel", c, k, 0, 3, both, true); }
+
 int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
                 uint64_t n_regions) {
     kp_seq_sess *s = seq_sess(c);
@@ -305,7 +327,10 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
             for (uint64_t p = b0; p < b0 + it.count + (uint64_t)k - 1; ++p) {
                 kp_s_step(w, kp_s_class(seq[p]), mask, 2 * (k - 1));
                 if (w.valid >= (uint32_t)k) {
-                    ++bg[kp_s_code(w, k, s->fold)];
+                    if (s->both)
+                        ++bg[w.fwd], ++bg[w.rc];
+                    else
+                        ++bg[kp_s_code(w, k, s->fold)];
                     ++s->st.windows;
                 }
             }
@@ -340,10 +365,29 @@ int kp_seq_scan(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *reg_b
         A.cells = (uint32_t)s->cells;
         A.tab = s->d_tab + (uint64_t)s->pcols * s->cells;
         A.stat = s->d_stat;
+        const bool merge = env_int("KP_SEQ_MERGE", 1) != 0;  // (on by measurement: a quarter faster on a repeat-rich contig)
         KP_HIP(hipEventRecord(c->ev[0], st));
-        if (lds)
+        if (s->both) {
+            // LDS counters: at most max_steps items per workgroup and launch (kp_seq_scan_kernel)
+            const long steps_env = env_int("KP_SEQ_BOTH_STEPS", KP_S_BOTH_STEPS);
+            if (steps_env < 1 || steps_env > (long)KP_S_BOTH_STEPS)
+                return fail(KP_E_ARG, "kp_seq_scan: KP_SEQ_BOTH_STEPS must be 1..131072 (a uint32 LDS counter takes 2 per centre)");
+            const uint64_t max_steps = lds ? (uint64_t)steps_env : steps, per_launch = grid * max_steps;
+            for (uint64_t i0 = 0; i0 < items.size(); i0 += per_launch) {
+                const uint64_t cnt = std::min<uint64_t>(per_launch, items.size() - i0);
+                A.items = d_items + i0;
+                A.n_items = (uint32_t)cnt;
+                A.steps = (uint32_t)((cnt + grid - 1) / grid);
+                if (lds)
+                    hipLaunchKernelGGL((kp_seq_scan_kernel<true, false, true>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
+                else if (merge)
+                    hipLaunchKernelGGL((kp_seq_scan_kernel<false, true, true>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
+                else
+                    hipLaunchKernelGGL((kp_seq_scan_kernel<false, false, true>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
+            }
+        } else if (lds)
             hipLaunchKernelGGL((kp_seq_scan_kernel<true, false>), dim3((unsigned)grid), dim3(KP_S_THREADS), lds_bytes, st, A);
-        else if (env_int("KP_SEQ_MERGE", 1) != 0)  // (on by measurement: a quarter faster on a repeat-rich contig)
+        else if (merge)
             hipLaunchKernelGGL((kp_seq_scan_kernel<false, true>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
         else
             hipLaunchKernelGGL((kp_seq_scan_kernel<false, false>), dim3((unsigned)grid), dim3(KP_S_THREADS), 0, st, A);
@@ -368,6 +412,8 @@ int kp_seq_sites(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t *pos,
     kp_seq_sess *s = seq_sess(c);
     int rc = scan_check_contig("kp_seq_sites", s->active, seq, n, "kp_seq_begin");
     if (rc) return rc;
+    if (s->indel) return fail(KP_E_STATE, "kp_seq_sites: the session is an indel session (kp_seq_indels)");
+    if (s->both) return fail(KP_E_STATE, "kp_seq_sites: the session counts both strands, which single-base sites have no rule for");
     if (s->pcols != 1) return fail(KP_E_STATE, "kp_seq_sites: the session is typed (kp_seq_sites_typed)");
     if (n_sites && !pos) return fail(KP_E_ARG, "kp_seq_sites: null positions");
     if (n_sites >= (1ull << 39)) return fail(KP_E_ARG, "kp_seq_sites: 2^39 sites or more in one call");

@@ -718,6 +718,7 @@ int kp_seq_sites_typed(kp_ctx *c, const uint8_t *seq, uint64_t n, const uint64_t
     kp_seq_sess *s = seq_sess(c);
     int rc = scan_check_contig("kp_seq_sites_typed", s->active, seq, n, "kp_seq_begin");
     if (rc) return rc;
+    if (s->indel) return fail(KP_E_STATE, "kp_seq_sites_typed: the session is an indel session (kp_seq_indels)");
     if (s->pcols != 3) return fail(KP_E_STATE, "kp_seq_sites_typed: the session is not typed (kp_seq_begin_typed)");
     if ((rc = spec_check_sites("kp_seq_sites_typed", n, pos, alt, n_sites))) return rc;
     if (!n_sites) return KP_OK;

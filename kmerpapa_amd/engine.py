@@ -130,7 +130,10 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_seq_sites_typed", "kp_seq_end_typed", "kp_spec_begin", "kp_spec_regions", "kp_spec_track",
            "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim",
            "kp_spec_null", "kp_spec_last_null", "kp_spec_coding", "kp_spec_coding_sites", "kp_spec_last_coding",
-           "kp_spec_coding_null", "kp_spec_last_coding_null"]
+           "kp_spec_coding_null", "kp_spec_last_coding_null", "kp_seq_begin_indel", "kp_seq_begin_strands",
+           "kp_seq_indels", "kp_seq_indel_host"]
+
+INDEL_PLACE = {"left": 0, "right": 1, "sample": 2}  # kp_seq_indels' place
 
 
 def load():
@@ -253,6 +256,14 @@ def load():
             L.kp_spec_coding_null.argtypes = [vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, u32, vp, ctypes.c_double, u64, u32,
                                               u32, vp]
             L.kp_spec_last_coding_null.argtypes = [vp, ctypes.POINTER(KPSpecCodingNullStats)]
+        if hasattr(L, "kp_seq_indels"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            L.kp_seq_begin_indel.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+            L.kp_seq_begin_strands.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+            sites = [vp, vp, vp, vp, vp, u64, ctypes.c_int, u64]  # pos, del_len, key, ins_off, ins, n, place, seed
+            L.kp_seq_indels.argtypes = [vp, vp, u64, u32] + sites + [vp]
+            L.kp_seq_indel_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, u32, ctypes.c_int, vp, vp, u64] + sites + \
+                [vp, vp, vp, ctypes.POINTER(KPSeqStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -629,6 +640,88 @@ class _SeqCalls:
         return pos, bg, self.seq_stats()
 
 
+    def seq_begin_indel(self, k, both=True):
+        """Open an indel session of even ``k`` (kp_seq_begin_indel): columns ins, del_start and
+        del_end beside the background; ``both``: every add comes with its mirror on the other strand."""
+        _check(load().kp_seq_begin_indel(self._h, int(k), int(bool(both))))
+        self._seq_cells = 4 ** int(k)
+
+    def seq_begin_strands(self, k, both=True):
+        """Open a plain, unfolded session whose scan adds on both strands if ``both``
+        (kp_seq_begin_strands); :meth:`seq_end` closes it."""
+        _check(load().kp_seq_begin_strands(self._h, int(k), int(bool(both))))
+        self._seq_cells = 4 ** int(k)
+
+    def seq_indels(self, seq, contig, sites, place="left", seed=0, want_resolved=True):
+        """Place and count the indels ``sites`` (:func:`indel_sites`) of the contig ``seq`` with index
+        ``contig`` (kp_seq_indels).  Returns ``resolved`` uint64 ``[m, 3]``: lo, hi and the chosen
+        breakpoint of every site, or None."""
+        seq, n = _seq_bytes(seq)
+        pos, del_len, ins, ins_off, key = sites
+        res = np.zeros((pos.shape[0], 3), np.uint64) if want_resolved else None
+        _check(load().kp_seq_indels(self._h, _ptr(seq), n, int(contig), _ptr(pos), _ptr(del_len), _ptr(key), _ptr(ins_off),
+                                    _ptr(ins), ctypes.c_uint64(pos.shape[0]), INDEL_PLACE[place], ctypes.c_uint64(int(seed)),
+                                    _ptr(res)))
+        return res
+
+    def seq_count_indels(self, k, both, jobs, place="left", seed=0):
+        """One whole indel session.  ``jobs``: one ``(seq, regions, contig index, sites)`` per contig,
+        ``regions`` as :meth:`seq_count`'s, ``sites`` an :func:`indel_sites` tuple or None.  Returns
+        ``(pos_counts [3, 4^k], bg_counts, stats, [resolved or None per job])``."""
+        self.seq_begin_indel(k, both)
+        resolved = []
+        try:
+            for seq, regions, contig, sites in jobs:
+                if regions is not False:
+                    self.seq_scan(seq, regions)
+                resolved.append(self.seq_indels(seq, contig, sites, place, seed)
+                                if sites is not None and len(sites[0]) else None)
+        except BaseException:
+            self.seq_end_typed(False, False)
+            raise
+        pos, bg = self.seq_end_typed()
+        return pos, bg, self.seq_stats(), resolved
+
+    def seq_count_strands(self, k, both, jobs):
+        """One whole background session of both strands (or, ``both`` False, of the forward strand
+        unfolded).  ``jobs``: one ``(seq, regions)`` per contig.  Returns ``(bg_counts, stats)``."""
+        self.seq_begin_strands(k, both)
+        try:
+            for seq, regions in jobs:
+                if regions is not False:
+                    self.seq_scan(seq, regions)
+        except BaseException:
+            self.seq_end(False, False)
+            raise
+        _, bg = self.seq_end(False, True)
+        return bg, self.seq_stats()
+
+
+def indel_sites(pos, del_len, insertions, key=None):
+    """The arrays kp_seq_indels takes: ``pos`` and ``del_len`` (0 = an insertion) per site,
+    ``insertions`` one bytes / str per site (empty for a deletion) or an ``(ins uint8 pool, ins_off
+    uint64 [m + 1])`` pair, ``key`` per site (None: the site's index)."""
+    pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+    del_len = np.ascontiguousarray(del_len, dtype=np.uint64).reshape(-1)
+    if isinstance(insertions, tuple):
+        ins, ins_off = insertions
+    else:
+        parts = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in insertions]
+        ins = np.frombuffer(b"".join(parts), np.uint8)
+        ins_off = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
+    ins = np.ascontiguousarray(ins, dtype=np.uint8).reshape(-1)
+    ins_off = np.ascontiguousarray(ins_off, dtype=np.uint64).reshape(-1)
+    if del_len.shape[0] != pos.shape[0] or ins_off.shape[0] != pos.shape[0] + 1:
+        raise ValueError("one deletion length and one insertion per site")
+    if int(ins_off[-1]) != ins.shape[0]:
+        raise ValueError("the last insertion offset is the size of the pool")
+    if key is not None:
+        key = np.ascontiguousarray(key, dtype=np.uint64).reshape(-1)
+        if key.shape[0] != pos.shape[0]:
+            raise ValueError("one key per site")
+    return pos, del_len, ins, ins_off, key
+
+
 class HostSeq(_SeqCalls):
     """The kp_seq_* calls of the calling thread's host session (ctx = NULL): the kernels' per-base
     code run serially on the host (parity and CPU tests, not a product path)."""
@@ -657,6 +750,29 @@ def seq_host_contig(k, fold, seq, regions=None, sites=None):
     _check(load().kp_seq_host(int(k), int(bool(fold)), _ptr(seq), n, int(scan), _ptr(rb), _ptr(re), ctypes.c_uint64(nr),
                               _ptr(p), ctypes.c_uint64(p.shape[0]), _ptr(pos), _ptr(bg), ctypes.byref(st)))
     return pos, bg, {name: getattr(st, name) for name, _ in KPSeqStats._fields_}
+
+
+def seq_indel_host_contig(k, both, seq, contig, regions=None, sites=None, place="left", seed=0):
+    """One host indel session of one contig in one call (kp_seq_indel_host); arguments as
+    :meth:`Device.seq_count_indels`'s jobs.  Returns ``(pos_counts [3, 4^k], bg_counts, stats,
+    resolved)``."""
+    seq, n = _seq_bytes(seq)
+    rb = re = None
+    nr = 0
+    scan = regions is not False
+    if scan and regions is not None:
+        rb, re, nr = _regions_arrays(regions)
+        scan = nr > 0
+    pos, del_len, ins, ins_off, key = sites if sites is not None else indel_sites([], [], [])
+    cells = 4 ** int(k) if 1 <= int(k) <= 15 else 1
+    cols, bg = np.zeros((3, cells), np.uint64), np.zeros(cells, np.uint64)
+    res = np.zeros((pos.shape[0], 3), np.uint64)
+    st = KPSeqStats()
+    _check(load().kp_seq_indel_host(int(k), int(bool(both)), _ptr(seq), n, int(contig), int(scan), _ptr(rb), _ptr(re),
+                                    ctypes.c_uint64(nr), _ptr(pos), _ptr(del_len), _ptr(key), _ptr(ins_off), _ptr(ins),
+                                    ctypes.c_uint64(pos.shape[0]), INDEL_PLACE[place], ctypes.c_uint64(int(seed)),
+                                    _ptr(cols), _ptr(bg), _ptr(res), ctypes.byref(st)))
+    return cols, bg, {name: getattr(st, name) for name, _ in KPSeqStats._fields_}, res
 
 
 def _regions_arrays(regions):

@@ -308,6 +308,117 @@ def read_sites_alt(path_or_file):
             for name, (p, r, a) in per.items()}, stats
 
 
+def trim_alleles(ref, alt):
+    """REF and ALT without their longest common prefix and then, of what is left, their longest
+    common suffix: ``(prefix length, ref, alt)``."""
+    q = 0
+    while q < len(ref) and q < len(alt) and ref[q] == alt[q]:
+        q += 1
+    ref, alt = ref[q:], alt[q:]
+    t = 0
+    while t < len(ref) and t < len(alt) and ref[-1 - t] == alt[-1 - t]:
+        t += 1
+    return q, ref[:len(ref) - t], alt[:len(alt) - t]
+
+
+class IndelSites:
+    """The indels of one contig in file order: 0-based ``pos`` (the breakpoint of an insertion, the
+    first deleted base of a deletion), ``del_len`` (0 = an insertion), the inserted strings as one
+    upper-case pool ``ins`` with offsets ``ins_off`` ``[m + 1]``, ``key`` (the 0-based number of the
+    site's line in its file) and, for :func:`match_indel_ref`, the whole REF as spelled: ``ref``
+    pool, ``ref_off`` ``[m + 1]`` and its 0-based position ``ref_pos``."""
+
+    def __init__(self, pos, del_len, ins, ins_off, key, ref_pos, ref, ref_off):
+        self.pos, self.del_len, self.ins, self.ins_off, self.key = pos, del_len, ins, ins_off, key
+        self.ref_pos, self.ref, self.ref_off = ref_pos, ref, ref_off
+
+    def __len__(self):
+        return self.pos.shape[0]
+
+    def arrays(self):
+        """What ``engine.Device.seq_indels`` takes."""
+        return self.pos, self.del_len, self.ins, self.ins_off, self.key
+
+    def take(self, keep):
+        """The sites where the bool array ``keep`` is set."""
+        def pool(data, off):
+            off = off.astype(np.int64)
+            lens = (off[1:] - off[:-1])[keep]
+            idx = np.repeat(off[:-1][keep], lens) + (np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens))
+            return data[idx], np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+
+        ins, ins_off = pool(self.ins, self.ins_off)
+        ref, ref_off = pool(self.ref, self.ref_off)
+        return IndelSites(self.pos[keep], self.del_len[keep], ins, ins_off, self.key[keep], self.ref_pos[keep], ref, ref_off)
+
+
+def read_indels(path_or_file):
+    """``CHROM POS REF ALT`` lines (1-based POS; further columns ignored, ``#`` lines skipped; ``-``
+    or ``.`` spells an empty allele) that are short insertions or deletions.  REF and ALT lose their
+    longest common prefix, then the longest common suffix of the rest (:func:`trim_alleles`);
+    exactly one of them must be empty afterwards: an insertion of ALT before the base POS + prefix,
+    or a deletion of REF from there.  Everything else is counted and dropped: ``not_indel`` (an SNV,
+    REF == ALT, a symbolic or comma-separated ALT, a letter other than ACGT in an insertion or in
+    either allele's spelling) or ``complex`` (both left non-empty: MNVs and delins).
+    Returns ``({chrom: IndelSites}, stats)``, ``stats`` counting ``lines``, ``not_indel`` and
+    ``complex``.  A site's key is the 0-based number of its line in the file (every line counts)."""
+    per = {}
+    stats = {"lines": 0, "not_indel": 0, "complex": 0}
+    for number, line in enumerate(_read_all(path_or_file).decode("ascii", errors="replace").splitlines()):
+        tok = line.split()
+        if not tok or tok[0].startswith("#"):
+            continue
+        if len(tok) < 4:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}")
+        try:
+            pos = int(tok[1])
+        except ValueError:
+            raise ValueError(f"bad sites line (CHROM POS REF ALT):\n{line.strip()}") from None
+        if pos < 1:
+            raise ValueError(f"POS is 1-based:\n{line.strip()}")
+        stats["lines"] += 1
+        ref, alt = ("" if x in ("-", ".") else x.upper() for x in tok[2:4])
+        if any(c not in _COMPLEMENT for c in ref + alt):  # (symbolic <DEL>, *, commas, IUPAC letters)
+            stats["not_indel"] += 1
+            continue
+        q, r, a = trim_alleles(ref, alt)
+        if r and a:
+            stats["not_indel" if len(r) == 1 and len(a) == 1 else "complex"] += 1
+            continue
+        if not r and not a:
+            stats["not_indel"] += 1
+            continue
+        lists = per.setdefault(tok[0], ([], [], [], [], [], []))
+        for lst, v in zip(lists, (pos - 1 + q, len(r), a, number, pos - 1, ref)):
+            lst.append(v)
+    out = {}
+    for name, (p, dl, ins, key, rp, ref) in per.items():
+        def pool(strings):
+            off = np.concatenate([[0], np.cumsum([len(x) for x in strings])]).astype(np.uint64)
+            return np.frombuffer("".join(strings).encode("ascii"), np.uint8), off
+
+        out[name] = IndelSites(np.array(p, np.uint64), np.array(dl, np.uint64), *pool(ins), np.array(key, np.uint64),
+                               np.array(rp, np.uint64), *pool(ref))
+    return out, stats
+
+
+def match_indel_ref(seq, sites):
+    """The :class:`IndelSites` that lie on the contig ``seq`` and whose whole REF equals the contig
+    there case-insensitively: ``(kept sites, n_off_contig, n_ref_mismatch)``.  A site is off the
+    contig if its REF, its breakpoint or its deleted bases reach past the end."""
+    n = np.uint64(seq.shape[0])
+    ref_len = sites.ref_off[1:] - sites.ref_off[:-1]
+    on = (sites.ref_pos + ref_len <= n) & (sites.pos + sites.del_len <= n)
+    lens = np.where(on, ref_len, np.uint64(0)).astype(np.int64)  # (a site off the contig compares nothing)
+    start = np.cumsum(lens) - lens
+    within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(start, lens)
+    at = np.repeat(sites.ref_pos.astype(np.int64), lens) + within
+    want = sites.ref[np.repeat(sites.ref_off[:-1].astype(np.int64), lens) + within]
+    wrong = np.concatenate([[0], np.cumsum((seq[at] & 0xDF) != want)])
+    same = wrong[start + lens] == wrong[start]
+    return sites.take(on & same), int((~on).sum()), int((on & ~same).sum())
+
+
 def match_ref(seq, pos, ref):
     """The positions of ``pos`` that lie on the contig ``seq`` and whose base there equals
     ``ref`` case-insensitively: ``(kept positions, n_off_contig, n_ref_mismatch)``."""

@@ -802,6 +802,93 @@ int kp_spec_coding_null(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t co
                         uint32_t n_reps, uint32_t *counts);
 int kp_spec_last_coding_null(kp_ctx *ctx, kp_spec_coding_null_stats *out);
 
+/* An indel model taken back to the genome on both strands: an insertion and a deletion partition,
+ * fitted on the ins and del_start columns of a both-strand indel session, applied per breakpoint.
+ * (No reference counterpart.)  Bases, windows, validity and codes are kp_seq's above, pattern words
+ * and matching kp_apply's; breakpoints and windows are those of the indel counting block: the
+ * window of breakpoint b at k = 2r is W(b) = seq[b - r, b + r).
+ * Strands.  del_start of a both-strand session means "a deletion begins here, read 5' to 3'": on the
+ * forward strand the rate of a deletion starting at b is r(W(b)), and r(rc(W(b))) is the rate of one
+ * ending at b.  A fitted partition is not rc-symmetric even where its table is (the lattice does not
+ * force P and rc(P) into one partition), so an insertion rate needs both look-ups as well.  Strand
+ * 0 of a result is the look-up of W(b), strand 1 that of rc(W(b)).
+ *   kp_ispec_begin   k even, 2..14; patterns[n_patterns] of both kinds in one list, pkind[p] = 0
+ *                    (ins) or 1 (del); a kind may have no pattern.  KP_E_ARG, naming the first
+ *                    offender: a pattern with an empty position or bits above position k, a kind out
+ *                    of range, two patterns of one kind that share a k-mer (across kinds is fine),
+ *                    n_patterns = 0.  Builds lut[4^k] of 16-byte entries {ins pattern of c, ins
+ *                    pattern of rc(c), del pattern of c, del pattern of rc(c)}, ids indexing
+ *                    `patterns`, -1 = none, in the context's arena (4 GiB at k = 14): the reverse
+ *                    complement is resolved when the table is built, so the scan pays one 16-byte
+ *                    gather per breakpoint and needs only the forward code.  The arena rules, the
+ *                    exclusions (kp_greedy, kp_apply, kp_seq_begin*, kp_pred_begin, kp_spec_begin and
+ *                    kp_ispec_begin during it are KP_E_STATE, and so is kp_ispec_begin during a
+ *                    kp_seq, kp_pred or kp_spec session; device contexts only) and KP_E_NOMEM are
+ *                    kp_spec_begin's.
+ *   kp_ispec_regions regions and clipping as kp_pred_regions': any order, overlapping or not, each
+ *                    one output row; a region's breakpoints are begin <= b < end.
+ *                    hist[n_regions][2][n_patterns] (may be NULL): strand 0 counts the breakpoints
+ *                    whose window matches the pattern, strand 1 those whose window's reverse
+ *                    complement matches it.  other[n_regions][5]: [2 * kind + strand] valid windows
+ *                    with no pattern of that kind on that strand, [4] windows that hold an invalid
+ *                    byte or run off the contig.  For every region, kind and strand the hist entries
+ *                    of that kind, other[2 * kind + strand] and other[4] sum to end - begin.  With
+ *                    rates[n_patterns] (may be NULL, then expected is not written)
+ *                    expected[n_regions][4] = ins forward, ins rc, del start (strand 0), del end
+ *                    (strand 1), each acc after acc = 0.0; for p ascending of that kind: acc = acc +
+ *                    (double)hist[r][strand][p] * rates[p].  The counters live in the arena during
+ *                    the call: KP_E_NOMEM if they do not fit.
+ *   kp_ispec_track   pid[4][end - begin], plane-major in the order of the table entry; values as
+ *                    kp_pred_track's: id, -1 for none, -2 for an invalid window.
+ *   kp_ispec_sites   site arrays, argument checks, equivalence interval, placement and its Philox
+ *                    draw are exactly kp_seq_indels'.  resolved[n_sites][3] (may be NULL) = lo, hi, p,
+ *                    identical to what a counting session returns for the same (place, seed, contig,
+ *                    key).  pid[n_sites][2]: for an insertion the ins pattern of W(p) and of rc(W(p));
+ *                    for a deletion the del pattern of W(p), its start, and of rc(W(p + L)), its end
+ *                    read on the other strand; -1 where no pattern matches; both -2 where the
+ *                    counting would skip the site whole (placed first, checked after, never
+ *                    re-placed).
+ *   kp_ispec_end, kp_ispec_last_stats  as kp_spec's; in the stats a breakpoint counts once per kind
+ *                    and strand: assigned + unmatched = 4 x the breakpoints with a valid window.
+ * Any call out of order is KP_E_STATE.  With ctx = NULL the calls run this thread's host session,
+ * serially with the same per-base and per-code functions; kp_ispec_host is one whole host session of
+ * one contig, as kp_spec_host (the sites with contig index `contig`).
+ * The scan is kp_spec's with fold = 0, one 16-byte gather and up to four counter adds per valid
+ * window: 2 x n_patterns uint32 LDS counters per item (strand-major) when n_patterns <= 8,192 -- the
+ * spectrum scan's 64 KiB -- and global 64-bit atomics otherwise.  The sites kernel runs
+ * kp_seq_indels' wave-cooperative interval search, then two table look-ups per site and no atomics
+ * on tables.  Knobs, read at each call (every setting gives the same results): KP_ISPEC_GLOBAL,
+ * KP_ISPEC_LDS_P (0..8192) and KP_ISPEC_GRID, with the meaning of their KP_SPEC_* counterparts. */
+typedef struct {
+    uint64_t assigned;      /* (breakpoint, kind, strand) triples of the regions calls with a pattern   */
+    uint64_t unmatched;     /* ... with a valid window and no pattern of the kind on the strand         */
+    uint64_t invalid;       /* breakpoints with an invalid byte in the window, or a window off the contig */
+    uint64_t items;         /* work items of the regions and track calls                                */
+    uint64_t lut_bytes;     /* size of the lookup table                                                 */
+    double lut_ms;          /* device time of the table's last build (HIP events; 0 on the host)        */
+    double scan_ms;         /* device time of the regions and track kernels (HIP events)                */
+    uint32_t tile;          /* breakpoints per work item at most                                        */
+    uint32_t path;          /* of the last regions call: 0 none or host, 1 LDS counters, 2 global atomics */
+    uint64_t sites;         /* sites of the sites calls that got their patterns                         */
+    uint64_t sites_skipped; /* ... skipped whole (both ids -2)                                          */
+    double sites_ms;        /* device time of the sites kernel (HIP events; 0 on the host)              */
+} kp_ispec_stats;
+int kp_ispec_begin(kp_ctx *ctx, int k, const uint64_t *patterns, const uint32_t *pkind, uint32_t n_patterns);
+int kp_ispec_regions(kp_ctx *ctx, const uint8_t *seq, uint64_t n, const uint64_t *reg_begin, const uint64_t *reg_end,
+                     uint64_t n_regions, const double *rates, uint64_t *hist, uint64_t *other, double *expected);
+int kp_ispec_track(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint64_t begin, uint64_t end, int32_t *pid);
+int kp_ispec_sites(kp_ctx *ctx, const uint8_t *seq, uint64_t n, uint32_t contig, const uint64_t *pos,
+                   const uint64_t *del_len, const uint64_t *key, const uint64_t *ins_off, const uint8_t *ins,
+                   uint64_t n_sites, int place, uint64_t seed, uint64_t *resolved, int32_t *pid);
+int kp_ispec_end(kp_ctx *ctx);
+int kp_ispec_last_stats(kp_ctx *ctx, kp_ispec_stats *out);
+int kp_ispec_host(int k, const uint64_t *patterns, const uint32_t *pkind, uint32_t n_patterns, const uint8_t *seq, uint64_t n,
+                  uint32_t contig, const uint64_t *reg_begin, const uint64_t *reg_end, uint64_t n_regions,
+                  const double *rates, uint64_t *hist, uint64_t *other, double *expected, uint64_t track_begin,
+                  uint64_t track_end, int32_t *track_pid, const uint64_t *pos, const uint64_t *del_len, const uint64_t *key,
+                  const uint64_t *ins_off, const uint8_t *ins, uint64_t n_sites, int place, uint64_t seed,
+                  uint64_t *resolved, int32_t *site_pid, kp_ispec_stats *stats);
+
 /* Host-only (no GPU needed): the cross-validation fold split of CV_tools.py
  * make_all_folds_contextD_patterns :44-57 / sample :5-27 with numpy's legacy
  * RandomState stream.  mt_key[624] / *mt_pos = the MT19937 state of the caller's

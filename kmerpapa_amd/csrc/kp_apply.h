@@ -301,6 +301,7 @@ int kp_apply(kp_ctx *c, int k, const uint64_t *patterns, uint32_t n_patterns, ui
     if (c->seq.active) return fail(KP_E_STATE, "kp_apply: a kp_seq session holds the context's arena (kp_seq_end first)");
     if (c->pred.active) return fail(KP_E_STATE, "kp_apply: a kp_pred session holds the context's arena (kp_pred_end first)");
     if (c->spec.active) return fail(KP_E_STATE, "kp_apply: a kp_spec session holds the context's arena (kp_spec_end first)");
+    if (c->ispec.active) return fail(KP_E_STATE, "kp_apply: a kp_ispec session holds the context's arena (kp_ispec_end first)");
     const uint32_t P = n_patterns;
     int rc = apply_check("kp_apply", k, patterns, P, super_word, codes, M, U, n, ncol, rates, pat_M, pat_U, ll, stats);
     if (rc) return rc;

@@ -119,6 +119,7 @@ int kp_greedy(kp_ctx *c, const char *gen_pat, const uint64_t *M, const uint64_t 
     if (c->seq.active) return fail(KP_E_STATE, "kp_greedy: a kp_seq session holds the context's arena (kp_seq_end first)");
     if (c->pred.active) return fail(KP_E_STATE, "kp_greedy: a kp_pred session holds the context's arena (kp_pred_end first)");
     if (c->spec.active) return fail(KP_E_STATE, "kp_greedy: a kp_spec session holds the context's arena (kp_spec_end first)");
+    if (c->ispec.active) return fail(KP_E_STATE, "kp_greedy: a kp_ispec session holds the context's arena (kp_ispec_end first)");
     kp_g_root R;
     std::vector<uint64_t> totM, totU;
     int n_chains = 0;

@@ -43,6 +43,10 @@
 //   kp_spec_*        every mutation type's partition in one pass (kp_spec.h): a table of 16-byte
 //                      entries (one pattern per ALT slot), the kp_pred roll with one gather and up
 //                      to three adds per window; typed site counting into three positive columns
+//   kp_ispec_*       an indel model on both strands (kp_ispec.h): a table of 16-byte entries (the ins
+//                      and the del pattern of a code and of its reverse complement), the kp_spec roll
+//                      with one gather and up to four adds per breakpoint; per site, kp_indel's
+//                      interval search and two table look-ups
 //   kp_sim_*         a random mutation set drawn from a spectrum model (kp_sim.h): the kp_spec roll,
 //                      one counter-based random number per position and an ordered two-pass
 //                      compaction of the hits
@@ -78,6 +82,8 @@
 //                  kp_spec_coding and kp_spec_coding_sites
 //   kp_indel.h     breakpoint contexts of indels: the equivalence interval of a site searched 64
 //                  positions per wave step, its placement and adds, kp_seq_indels
+//   kp_ispec.h     an insertion and a deletion partition applied per breakpoint on both strands: the
+//                  table of four ids per code, the scan, track and sites kernels, the kp_ispec_* sessions
 //   kp_folds.h, kp_io.h, kp_out.h   fold sampler, count-file parser, row writer
 #include "kp_rt.h"
 
@@ -103,6 +109,7 @@
 #include "kp_spec.h"
 #include "kp_sim.h"
 #include "kp_indel.h"
+#include "kp_ispec.h"
 #include "kp_null.h"
 #include "kp_coding.h"
 #include "kp_cnull.h"

@@ -150,6 +150,23 @@ struct kp_spec_sess {
     kp_spec_coding_null_stats cnull{};  // of the last kp_spec_coding_null call (kp_cnull.h)
 };
 
+// One kp_ispec_* session (kp_ispec.h): as kp_spec_sess, with the insertion and the deletion partition
+// in one pattern list and a table of 16-byte entries {ins pattern of c, ins pattern of rc(c), del
+// pattern of c, del pattern of rc(c)} per k-mer code c.
+struct kp_ispec_sess {
+    bool active = false;
+    bool lut_ok = false;  // d_lut holds the table of `pats`
+    int k = 0;
+    uint64_t cells = 0;  // 4^k
+    std::vector<uint64_t> pats;
+    std::vector<uint32_t> pkind;    // [P] 0 ins, 1 del
+    std::vector<uint32_t> by_kind;  // [P] the pattern indices grouped by kind, ascending within a kind
+    uint32_t kind_off[3] = {};      // by_kind[kind_off[t] .. kind_off[t + 1]) are the patterns of kind t
+    int32_t *d_lut = nullptr;       // [cells][4]
+    std::vector<int32_t> h_lut;
+    kp_ispec_stats st{};
+};
+
 #define KP_SIDE_STREAMS 3
 
 struct kp_ctx {
@@ -177,6 +194,8 @@ struct kp_ctx {
     kp_pred_sess pred;
     // kp_spec_*: the same for a whole mutation spectrum
     kp_spec_sess spec;
+    // kp_ispec_*: the same for an indel model
+    kp_ispec_sess ispec;
 };
 
 // What every genome scan session checks of a contig (kp_seq.h, kp_pred.h, kp_spec.h and the calls of

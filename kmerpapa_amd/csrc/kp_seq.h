@@ -230,6 +230,7 @@ static int seq_begin(const std::string &w, kp_ctx *c, int k, int fold, int pcols
     if (s->active) return fail(KP_E_STATE, w + ": a session is open (kp_seq_end first)");
     if (c && c->pred.active) return fail(KP_E_STATE, w + ": a kp_pred session holds the context's arena (kp_pred_end first)");
     if (c && c->spec.active) return fail(KP_E_STATE, w + ": a kp_spec session holds the context's arena (kp_spec_end first)");
+    if (c && c->ispec.active) return fail(KP_E_STATE, w + ": a kp_ispec session holds the context's arena (kp_ispec_end first)");
     if (indel && (k < 2 || k > 14 || k % 2))
         return fail(KP_E_ARG, w + ": k must be even and 2..14 (the window of a breakpoint has k/2 bases on each side)");
     if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, w + ": k must be 1..15 (a dense table of 4^k counters)");

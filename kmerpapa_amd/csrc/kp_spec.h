@@ -370,6 +370,8 @@ int kp_spec_begin(kp_ctx *c, int k, int fold, const uint64_t *patterns, const ui
         return fail(KP_E_STATE, "kp_spec_begin: a kp_seq session holds the context's arena (kp_seq_end first)");
     if (c && c->pred.active)
         return fail(KP_E_STATE, "kp_spec_begin: a kp_pred session holds the context's arena (kp_pred_end first)");
+    if (c && c->ispec.active)
+        return fail(KP_E_STATE, "kp_spec_begin: a kp_ispec session holds the context's arena (kp_ispec_end first)");
     if (k < 1 || k > KP_S_MAXK) return fail(KP_E_ARG, "kp_spec_begin: k must be 1..15 (a dense table of 4^k entries)");
     if (fold && k % 2 == 0) return fail(KP_E_ARG, "kp_spec_begin: strand folding needs an odd k (a centre base)");
     const uint32_t P = n_patterns;

@@ -114,9 +114,16 @@ class KPSpecCodingNullStats(ctypes.Structure):
                 ("stage_ms", ctypes.c_double), ("draw_ms", ctypes.c_double)]
 
 
+class KPISpecStats(ctypes.Structure):
+    _fields_ = list(KPPredStats._fields_) + [("sites", ctypes.c_uint64), ("sites_skipped", ctypes.c_uint64),
+                                             ("sites_ms", ctypes.c_double)]
+
+
 SEQ_PATH_LDS, SEQ_PATH_GLOBAL = 1, 2  # KPSeqStats.path of a device scan (0: host, or no scan yet)
 PRED_PATH_LDS, PRED_PATH_GLOBAL = 1, 2  # KPPredStats.path of a device regions call (0: host, or none yet)
 SPEC_PATH_LDS, SPEC_PATH_GLOBAL = 1, 2  # KPSpecStats.path, the same
+ISPEC_PATH_LDS, ISPEC_PATH_GLOBAL = 1, 2  # KPISpecStats.path, the same
+ISPEC_INS, ISPEC_DEL = 0, 1  # kp_ispec_begin's pattern kinds
 
 EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_device_mem", "kp_plan_create",
            "kp_plan_destroy", "kp_plan_get_info", "kp_plan_host", "kp_plan_host_counts", "kp_set_counts", "kp_counts_begin", "kp_counts_fold", "kp_pass",
@@ -131,7 +138,8 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_spec_sites", "kp_spec_end", "kp_spec_last_stats", "kp_spec_host", "kp_spec_simulate", "kp_spec_last_sim",
            "kp_spec_null", "kp_spec_last_null", "kp_spec_coding", "kp_spec_coding_sites", "kp_spec_last_coding",
            "kp_spec_coding_null", "kp_spec_last_coding_null", "kp_seq_begin_indel", "kp_seq_begin_strands",
-           "kp_seq_indels", "kp_seq_indel_host"]
+           "kp_seq_indels", "kp_seq_indel_host", "kp_ispec_begin", "kp_ispec_regions", "kp_ispec_track",
+           "kp_ispec_sites", "kp_ispec_end", "kp_ispec_last_stats", "kp_ispec_host"]
 
 INDEL_PLACE = {"left": 0, "right": 1, "sample": 2}  # kp_seq_indels' place
 
@@ -264,6 +272,17 @@ def load():
             L.kp_seq_indels.argtypes = [vp, vp, u64, u32] + sites + [vp]
             L.kp_seq_indel_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, u32, ctypes.c_int, vp, vp, u64] + sites + \
                 [vp, vp, vp, ctypes.POINTER(KPSeqStats)]
+        if hasattr(L, "kp_ispec_begin"):  # (older builds loaded through KMERPAPA_LIB for A/B timing lack it)
+            u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+            sites = [vp, vp, vp, vp, vp, u64, ctypes.c_int, u64]  # pos, del_len, key, ins_off, ins, n, place, seed
+            L.kp_ispec_begin.argtypes = [vp, ctypes.c_int, vp, vp, u32]
+            L.kp_ispec_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+            L.kp_ispec_track.argtypes = [vp, vp, u64, u64, u64, vp]
+            L.kp_ispec_sites.argtypes = [vp, vp, u64, u32] + sites + [vp, vp]
+            L.kp_ispec_end.argtypes = [vp]
+            L.kp_ispec_last_stats.argtypes = [vp, ctypes.POINTER(KPISpecStats)]
+            L.kp_ispec_host.argtypes = [ctypes.c_int, vp, vp, u32, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, u64, u64, vp] + \
+                sites + [vp, vp, ctypes.POINTER(KPISpecStats)]
         for name in EXPORTS:
             if not hasattr(L, name):
                 continue
@@ -1160,7 +1179,131 @@ def spec_host(k, patterns, ptype, fold, seq, regions=None, rates=None, track=Non
             {name: getattr(st, name) for name, _ in KPSpecStats._fields_})
 
 
-class Device(_SeqCalls, _PredCalls, _SpecCalls):
+def _stats_dict(st):
+    return {name: getattr(st, name) for name, _ in type(st)._fields_}
+
+
+class _ISpecCalls:
+    """The kp_ispec_* session calls on ``self._h``: a :class:`Device`'s context, or None for the
+    calling thread's host session (:class:`HostISpec`)."""
+
+    _h = None
+    _ispec_P = 0
+
+    def ispec_begin(self, k, patterns, pkind):
+        """Open an indel-model session of even ``k`` (kp_ispec_begin): ``patterns`` are the pattern
+        words of both kinds in one list, ``pkind`` their kinds (0 ins, 1 del); the patterns of one
+        kind must be pairwise disjoint."""
+        pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+        kind = np.asarray(pkind, dtype=np.int64).reshape(-1)
+        if kind.shape[0] != pats.shape[0]:
+            raise ValueError("one kind per pattern")
+        if np.any(kind < 0) or np.any(kind >= 1 << 32):
+            raise ValueError("a kind that is no uint32")
+        kind = np.ascontiguousarray(kind, dtype=np.uint32)
+        _check(load().kp_ispec_begin(self._h, int(k), _ptr(pats), _ptr(kind), ctypes.c_uint32(pats.shape[0])))
+        self._ispec_P = pats.shape[0]
+
+    def ispec_regions(self, seq, regions, rates=None, want_hist=True, budget=None):
+        """Per region of the contig ``seq`` (breakpoints ``begin <= b < end``): ``(hist, other,
+        expected)`` -- ``hist`` uint64 ``[m, 2, P]`` by strand (None without ``want_hist``), ``other``
+        uint64 ``[m, 5]`` = breakpoints without an ins pattern forward / rc, without a del pattern
+        forward / rc, and without a valid window, ``expected`` float64 ``[m, 4]`` = ins forward, ins
+        rc, del start, del end (None without ``rates``) (kp_ispec_regions).  With ``budget`` the
+        regions go in batches of at most that many counters a call, which changes no result."""
+        seq, n = _seq_bytes(seq)
+        rb, re, m = _regions_arrays(regions)
+        P = self._ispec_P
+        r = exp = None
+        if rates is not None:
+            r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+            if r.shape[0] != P:
+                raise ValueError("one rate per pattern")
+            exp = np.zeros((m, 4), np.float64)
+        hist = np.zeros((m, 2, P), np.uint64) if want_hist else None
+        other = np.zeros((m, 5), np.uint64)
+        step = m if budget is None else max(1, int(budget) // max(2 * P, 1))
+        for b in range(0, m, max(step, 1)):
+            e = min(m, b + step)
+            _check(load().kp_ispec_regions(self._h, _ptr(seq), n, _ptr(rb[b:e]), _ptr(re[b:e]), ctypes.c_uint64(e - b),
+                                           _ptr(r), _ptr(hist[b:e]) if want_hist else None, _ptr(other[b:e]),
+                                           _ptr(exp[b:e]) if exp is not None else None))
+        return hist, other, exp
+
+    def ispec_track(self, seq, begin=0, end=None):
+        """int32 ``[4, end - begin]``: per breakpoint the ins pattern of its window and of the
+        window's reverse complement, then the del patterns; -1 if none, -2 without a valid window
+        (kp_ispec_track)."""
+        seq, n = _seq_bytes(seq)
+        end = seq.shape[0] if end is None else int(end)
+        pid = np.zeros((4, max(end - int(begin), 0)), np.int32)
+        _check(load().kp_ispec_track(self._h, _ptr(seq), n, ctypes.c_uint64(int(begin)), ctypes.c_uint64(end), _ptr(pid)))
+        return pid
+
+    def ispec_sites(self, seq, contig, sites, place="left", seed=0, want_resolved=True):
+        """The two patterns of every indel of ``sites`` (:func:`indel_sites`) on the contig ``seq``
+        with index ``contig``, placed as :meth:`seq_indels` places it (kp_ispec_sites).  Returns
+        ``(pid int32 [m, 2], resolved uint64 [m, 3] or None)``: an insertion's ins pattern on the
+        forward and the other strand, a deletion's del pattern of its start and of its end; -1 none,
+        both -2 for a site the counting skips."""
+        seq, n = _seq_bytes(seq)
+        pos, del_len, ins, ins_off, key = sites
+        m = pos.shape[0]
+        res = np.zeros((m, 3), np.uint64) if want_resolved else None
+        pid = np.zeros((m, 2), np.int32)
+        _check(load().kp_ispec_sites(self._h, _ptr(seq), n, int(contig), _ptr(pos), _ptr(del_len), _ptr(key), _ptr(ins_off),
+                                     _ptr(ins), ctypes.c_uint64(m), INDEL_PLACE[place], ctypes.c_uint64(int(seed)),
+                                     _ptr(res), _ptr(pid)))
+        return pid, res
+
+    def ispec_end(self):
+        """Close the session (kp_ispec_end)."""
+        _check(load().kp_ispec_end(self._h))
+
+    def ispec_stats(self):
+        """Figures of the current or last session (kp_ispec_last_stats) as a dict."""
+        st = KPISpecStats()
+        _check(load().kp_ispec_last_stats(self._h, ctypes.byref(st)))
+        return _stats_dict(st)
+
+
+class HostISpec(_ISpecCalls, _SeqCalls):
+    """The kp_ispec_* (and kp_seq_*) calls of the calling thread's host session (ctx = NULL): the
+    kernels' per-base and per-code functions run serially on the host (parity and CPU tests, ``--host``)."""
+
+
+def ispec_host(k, patterns, pkind, seq, contig=0, regions=None, rates=None, track=None, sites=None, place="left", seed=0):
+    """One host session of one contig in one call (kp_ispec_host): the ``regions`` (with ``rates``),
+    the ``track`` range ``(begin, end)`` and the ``sites`` (:func:`indel_sites`), each optional.
+    Returns ``(hist, other, expected, track_pid, site_pid, resolved, stats)``."""
+    seq, n = _seq_bytes(seq)
+    pats = np.ascontiguousarray(patterns, dtype=np.uint64).reshape(-1)
+    kind = np.ascontiguousarray(pkind, dtype=np.uint32).reshape(-1)
+    P = pats.shape[0]
+    rb, re, m = _regions_arrays(regions if regions is not None else np.zeros((0, 2)))
+    r = exp = None
+    if rates is not None:
+        r = np.ascontiguousarray(rates, dtype=np.float64).reshape(-1)
+        if r.shape[0] != P:
+            raise ValueError("one rate per pattern")
+        exp = np.zeros((m, 4), np.float64)
+    hist, other = np.zeros((m, 2, P), np.uint64), np.zeros((m, 5), np.uint64)
+    tb, te = (0, 0) if track is None else (int(track[0]), int(track[1]))
+    tlen = max(te - tb, 0)
+    tpid = None if track is None else np.zeros(4 * tlen + 1, np.int32)  # (never a null pointer)
+    pos, del_len, ins, ins_off, key = sites if sites is not None else indel_sites([], [], [])
+    ns = pos.shape[0]
+    spid, res = np.zeros((ns, 2), np.int32), np.zeros((ns, 3), np.uint64)
+    st = KPISpecStats()
+    u64 = ctypes.c_uint64
+    _check(load().kp_ispec_host(int(k), _ptr(pats), _ptr(kind), ctypes.c_uint32(P), _ptr(seq), n, int(contig), _ptr(rb),
+                                _ptr(re), u64(m), _ptr(r), _ptr(hist), _ptr(other), _ptr(exp), u64(tb), u64(te), _ptr(tpid),
+                                _ptr(pos), _ptr(del_len), _ptr(key), _ptr(ins_off), _ptr(ins), u64(ns), INDEL_PLACE[place],
+                                u64(int(seed)), _ptr(res), _ptr(spid), ctypes.byref(st)))
+    return (hist, other, exp, None if tpid is None else tpid[:4 * tlen].reshape(4, tlen), spid, res, _stats_dict(st))
+
+
+class Device(_SeqCalls, _PredCalls, _SpecCalls, _ISpecCalls):
     """One HIP device context (stream + events) of the library."""
 
     def __init__(self, device=0):

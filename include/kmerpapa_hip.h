@@ -122,9 +122,12 @@ int kp_plan_host_counts(const char *gen_pat, uint32_t max_block, int itype_bytes
  * plan's block list (blocks by high level) from a closed-form rank rule.
  * kp_block_order_check, host-only: *mismatches = blocks whose closed-form slot differs from
  * the host's block walk.  kp_plan_block_check: *mismatches = entries of the plan's device
- * list that differ from the host walk. */
+ * list that differ from the host walk.  kp_block_list_host, host-only: the host walk's
+ * list itself, hlist[nblocks] (blocks in list order) and the level offsets
+ * hoff[high_levels + 1] into it (either may be null). */
 int kp_block_order_check(const char *gen_pat, uint32_t max_block, uint64_t *mismatches);
 int kp_plan_block_check(kp_plan *plan, uint64_t *mismatches);
+int kp_block_list_host(const char *gen_pat, uint32_t max_block, uint32_t *hlist, uint64_t *hoff);
 
 /* Upload fold counts of every k-mer: M, U are [n_kmers][nf] arrays of itype_bytes (4 or
  * 8) unsigned integers, k-mers in KmerEnumeration order (position 0 fastest, nucleotide

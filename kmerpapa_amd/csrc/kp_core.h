@@ -222,16 +222,31 @@ __host__ __device__ inline int kp_high_level(const kp_geom &g, const kp_postab *
 // the block order of kp::build_plan (high positions perm[0] fastest) in closed form
 struct kp_blockgen {
     int hs;                 // high level sums 0 .. hs - 1
+    int nfast;              // class order: perm[0 .. nfast) are the fast positions (0: plain order)
     int8_t perm[KP_MAXK];   // high positions, fastest first
+    // class order only, per fast position perm[j]
+    uint8_t nlev[KP_MAXK];      // its digit levels 0 .. nlev - 1
+    uint8_t share[KP_MAXK];     // bit l: the digits of level l have siblings (split pairs, several digits)
+    uint8_t lcnt[KP_MAXK][4];   // digits of level l
+    uint8_t didx[KP_MAXK][16];  // rank of digit d among the digits of its level
 };
 
-// Slot of block h in the plan's block list (blocks by high level, each level in the
-// mixed-radix order of perm) from build_plan's rank table brank[kh][16][hs] and level
-// offsets hoff; *hd / *hn = the block's packed high digits (4 bits) and split-pair counts
-// (3 bits per high position).  nblocks < 2^32 (build_plan), so 32-bit divisions suffice.
+// Slot of block h in the plan's block list (blocks by high level) from build_plan's rank
+// table brank[kh][16][hs] and level offsets hoff; *hd / *hn = the block's packed high digits
+// (4 bits) and split-pair counts (3 bits per high position).  nblocks < 2^32 (build_plan),
+// so 32-bit divisions suffice.
+// Plain order (bg.nfast == 0): each level in the mixed-radix order of perm.
+// Class order: inside a level the key is (slab = the digits of the slow positions
+// perm[nfast ..), in that mixed-radix order; class = the digit levels of the fast positions,
+// perm[nfast - 1] most significant; the fast digits without siblings; the fast digits with
+// siblings of level 1, then level 2, ..; every digit group with perm[0]'s side fastest).
+// The slab's rank is the plain order's rank terms of the slow positions (their inner count
+// is the number of fast digit tuples of a level sum), coff[class] = the fast tuples of the
+// classes before it with the same level sum, and the rest a mixed-radix rank over the
+// level sizes.
 __host__ __device__ inline uint64_t kp_block_slot(const kp_geom &g, const kp_postab *tabs, const kp_blockgen &bg,
-                                                  const uint32_t *brank, const uint64_t *hoff, uint64_t h,
-                                                  uint64_t *hd, uint64_t *hn) {
+                                                  const uint32_t *brank, const uint32_t *coff, const uint64_t *hoff,
+                                                  uint64_t h, uint64_t *hd, uint64_t *hn) {
     uint32_t dig[KP_MAXK];
     uint32_t s = 0;
     uint64_t w = 0, n = 0;
@@ -245,10 +260,26 @@ __host__ __device__ inline uint64_t kp_block_slot(const kp_geom &g, const kp_pos
     }
     uint64_t rank = 0;
     uint32_t above = 0;
-    for (int j = g.kh - 1; j >= 0; --j) {
+    for (int j = g.kh - 1; j >= bg.nfast; --j) {
         const int i = bg.perm[j];
         rank += brank[((uint32_t)j * 16u + dig[i]) * (uint32_t)bg.hs + (s - above)];
         above += tabs[g.t + i].lev[dig[i]];
+    }
+    if (bg.nfast > 0) {
+        uint32_t c = 0;
+        for (int j = bg.nfast - 1; j >= 0; --j) {
+            const int i = bg.perm[j];
+            c = c * bg.nlev[j] + tabs[g.t + i].lev[dig[i]];
+        }
+        uint64_t in = 0;
+        for (uint32_t grp = 0; grp < 4u; ++grp)  // 0: no siblings; l: siblings of level l
+            for (int j = bg.nfast - 1; j >= 0; --j) {
+                const int i = bg.perm[j];
+                const uint32_t l = tabs[g.t + i].lev[dig[i]];
+                const uint32_t mine = ((bg.share[j] >> l) & 1u) ? l : 0u;
+                if (mine == grp) in = in * bg.lcnt[j][l] + bg.didx[j][dig[i]];
+            }
+        rank += coff[c] + in;
     }
     *hd = w;
     *hn = n;

@@ -397,12 +397,16 @@ static int pass_params(kp_plan *p, const kp_geom &g, kp_dp_params *out) {
 #else
     P.dbg = 0;  // the product build has no phase-skipping path
 #endif
-    // runs of 40 consecutive blocks per XCD (workgroups are dealt round-robin over the 8
+    // runs of 36 consecutive blocks per XCD (workgroups are dealt round-robin over the 8
     // XCDs): neighbours in the reuse order share their L2; measured -1 % against none
     // (DESIGN.md §5), 16 against 8 -1.5 ms per 5-lane pass (12: -1.2, 32: -0.4), 24 against
     // 16 -1 ms (20: -0.5) and 40 against 24 -1 ms (32: +2, 64: +5; non-monotonic;
-    // profiles/r04/experiments/remap_ab.txt)
-    P.remap = (int)env_int("KP_XCD_REMAP", 40);
+    // profiles/r04/experiments/remap_ab.txt), all under the plain block order.  Under the
+    // class order (kp_plan.h) 36 against 40 -2.8 to -3.7 ms (24: -3.3, 64: +12), under the
+    // plain one 36 and 40 tie (profiles/block_class/ab.txt).  The cache model gives 36 and
+    // 40 the same traffic under the class order, so this step is measured, not modelled
+    // 
+    P.remap = (int)env_int("KP_XCD_REMAP", 36);
     P.lanesplit = (int)env_int("KP_LANE_SPLIT", 1);
     // KP_EXACT_LOGS=1: no fast device log at all (same results; exercises the exact path)
     P.exact = (int)env_int("KP_EXACT_LOGS", 0);
@@ -423,7 +427,10 @@ static int pass_params(kp_plan *p, const kp_geom &g, kp_dp_params *out) {
 // still in the Infinity Cache, so they no longer evict the rows of the fast positions
 // that are (9-mer pass 403-408 -> 397-398 ms; 2: 399-400, 4: 417)
 // KP_NT_SLOW_H = comma list: a count per high level (launch), for per-launch tuning;
-// levels past the list (or without it) take KP_NT_SLOW
+// levels past the list (or without it) take KP_NT_SLOW.
+// KP_NT_SLOW is also read by kp::build_plan, where it sets the slab of the class order of
+// the block list (the same slowest positions): changing it changes both the non-temporal
+// reads and the list.  KP_NT_SLOW_H changes the reads only; the slab does not follow it.
 static std::vector<uint32_t> nt_masks(const kp::host_plan &hp) {
     const kp_geom &g = hp.g;
     std::vector<uint32_t> ntmask_h(hp.hmax + 1, 0);

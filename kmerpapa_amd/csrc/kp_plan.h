@@ -18,6 +18,10 @@
 
 namespace kp {
 
+#ifndef KP_BLOCK_CLASS_DEFAULT
+#define KP_BLOCK_CLASS_DEFAULT 1  // the class order of the block list (build_plan); KP_BLOCK_CLASS=0/1 overrides
+#endif
+
 static const char *const kIupac = "ACGTRYSWKMBDHVN";
 static const char *const kNuc[15] = {"A", "C", "G", "T", "AG", "CT", "GC", "AT", "GT", "AC",
                                      "CGT", "AGT", "ACT", "ACG", "ACGT"};
@@ -61,6 +65,8 @@ struct host_plan {
     std::vector<int> perm;             // high positions of the block order, fastest first
     int hs = 0;                        // high level sums 0 .. hs - 1
     std::vector<uint32_t> brank;       // [kh][16][hs] rank table of the block order (build_plan)
+    int nfast = 0;                     // class order: perm[0 .. nfast) are the fast positions (0: plain order)
+    std::vector<uint32_t> coff;        // [classes] class offsets of the class order (kp_block_slot)
     bool blocks_on_host = true;        // hlist / kpos / hdig / hnp built here
     uint32_t kh_nuc_weight = 0;
     // algorithmic accounting: split pairs summed over all cells
@@ -298,6 +304,20 @@ inline std::string build_plan(const char *gen_pat, uint32_t max_block, host_plan
     // (position t fastest) +1 %, this order the best of those tried).
     // KP_BLOCK_PERM="5-4-..." (high positions, fastest first) and KP_BLOCK_ORDER=1
     // (shuffled) / KP_BLOCK_TILE=T override it for experiments.
+    // Class order (the default; KP_BLOCK_CLASS=0 restores the plain one): two blocks of a
+    // level share a child row along position p only if they are siblings -- all other
+    // digits equal, their digits at p on one level of p's code lattice (the six doubles of
+    // N share the four nucleotides, the four triples ten rows between them).  In the plain
+    // mixed-radix order a block's
+    // siblings along perm[1], perm[2] are 15 and 225 entries away.  Here the slow positions
+    // (the KP_NT_SLOW slowest of perm that have split pairs: the ones the sweep reads
+    // non-temporally) keep their order as the slab; inside a slab the blocks go by the
+    // vector of digit levels of the fast positions (the class), then by the fast digits
+    // that have no sibling, then by those that have, level 1 first, the highest level
+    // fastest -- so the sibling groups along every fast position sit in one short run
+    // (kp_block_slot has the key).  Measured with XCD runs of 36 blocks (kp_pass.h): 9-mer
+    // step 363.5 -> 357.8 ms; the fabric traffic and what the cache model does and does not
+    // explain of it are in DESIGN.md §5 and profiles/block_class/.
     std::vector<int> perm;
     if (const char *pe = getenv("KP_BLOCK_PERM")) {  // digits separated by any non-digit
         for (const char *c = pe; *c;) {
@@ -342,6 +362,40 @@ inline std::string build_plan(const char *gen_pat, uint32_t max_block, host_plan
     const uint32_t tile = te ? (uint32_t)atoi(te) : 0u;
     const char *bo = getenv("KP_BLOCK_ORDER");
     const bool shuffled = bo && atoi(bo) == 1;
+    // the class order's fast positions and class offsets: a digit has siblings when it has
+    // split pairs and its position another digit of its level; coff[c] = the fast digit
+    // tuples of the classes before c (perm[nfast - 1]'s level most significant) with c's
+    // level sum.  Off for a tiled / shuffled list and past 2^16 classes.
+    {
+        const char *ce = getenv("KP_BLOCK_CLASS");
+        const char *ne = getenv("KP_NT_SLOW");
+        int slow = ne ? atoi(ne) : 3, nfast = g.kh;
+        for (; nfast > 0 && slow > 0; --nfast)  // radix-1 positions (fixed bases) do not count
+            if (g.r[g.t + perm[nfast - 1]] > 1) --slow;
+        while (nfast > 0 && g.r[g.t + perm[nfast - 1]] == 1) --nfast;
+        uint64_t nc = 1;
+        for (int j = 0; j < nfast && nc <= 0x10000u; ++j) nc *= g.n[g.t + perm[j]];
+        if ((ce ? atoi(ce) : KP_BLOCK_CLASS_DEFAULT) != 0 && !tile && !shuffled && nfast > 0 && nc <= 0x10000u) {
+            P.nfast = nfast;
+            P.coff.assign((size_t)nc, 0);
+            std::vector<uint64_t> run(HS, 0);
+            for (uint64_t c = 0; c < nc; ++c) {
+                uint64_t q = c, size = 1;
+                int f = 0;
+                for (int j = 0; j < nfast; ++j) {
+                    const int i = g.t + perm[j];
+                    const uint32_t l = (uint32_t)(q % g.n[i]);
+                    q /= g.n[i];
+                    uint32_t cnt = 0;
+                    for (uint32_t d = 0; d < g.r[i]; ++d) cnt += P.tabs[i].lev[d] == l;
+                    size *= cnt;
+                    f += (int)l;
+                }
+                P.coff[c] = (uint32_t)run[f];
+                run[f] += size;
+            }
+        }
+    }
     P.blocks_on_host = block_tables || tile > 0 || shuffled;
     if (P.blocks_on_host) {
         // high levels of every block: a mixed-radix counter over h (high position 0 fastest)
@@ -423,6 +477,38 @@ inline std::string build_plan(const char *gen_pat, uint32_t max_block, host_plan
             }
             for (int s = 0; s <= hmax; ++s)
                 if (fill[s] != P.hoff[s + 1]) return "block order does not cover every block";
+            if (P.nfast > 0) {
+                // the class order by an explicit sort of every level of the walk's list
+                // (the check of kp_block_slot's closed form): three words per block, the
+                // slab's digits, the fast positions' levels, and the fast digits regrouped
+                // (no siblings | siblings of level 1 | level 2 | ..)
+                struct key3 { uint64_t slab, cls, dig; uint32_t h; };
+                std::vector<key3> keys(g.nblocks);
+                for (uint64_t q = 0; q < g.nblocks; ++q) {
+                    key3 K{0, 0, 0, P.hlist[q]};
+                    const uint64_t w = P.hdig[q];
+                    for (int j = g.kh - 1; j >= P.nfast; --j) K.slab = K.slab << 4 | ((w >> (4 * perm[j])) & 15u);
+                    for (int grp = 0; grp < 4; ++grp)
+                        for (int j = P.nfast - 1; j >= 0; --j) {
+                            const kp_postab &T = P.tabs[g.t + perm[j]];
+                            const uint32_t d = (uint32_t)(w >> (4 * perm[j])) & 15u, l = T.lev[d];
+                            if (grp == 0) K.cls = K.cls << 2 | l;
+                            uint32_t same = 0;
+                            for (uint32_t e = 0; e < g.r[g.t + perm[j]]; ++e) same += T.lev[e] == l;
+                            const bool sib = T.np[d] > 0 && same > 1;
+                            if ((sib ? (int)l : 0) == grp) K.dig = K.dig << 4 | d;
+                        }
+                    keys[q] = K;
+                }
+                for (int s = 0; s <= hmax; ++s)
+                    std::sort(keys.begin() + P.hoff[s], keys.begin() + P.hoff[s + 1], [](const key3 &a, const key3 &b) {
+                        if (a.slab != b.slab) return a.slab < b.slab;
+                        if (a.cls != b.cls) return a.cls < b.cls;
+                        return a.dig < b.dig;
+                    });
+                for (uint64_t q = 0; q < g.nblocks; ++q) P.hlist[q] = keys[q].h;
+                P.hdig.clear();  // recomputed below for the sorted list
+            }
             if (shuffled) P.hdig.clear();  // recomputed below for the shuffled list
             if (shuffled)
                 for (int s = 0; s <= hmax; ++s) {  // experiment: shuffled (no reuse order)

@@ -35,13 +35,13 @@ __global__ void kp_hpd_kernel(kp_geom g, const kp_postab *__restrict__ tabs, con
 // blocks at 9-mers: the walk was most of the plan's start-up, before the first pass).  One
 // thread per block h; every slot is written once (kp_block_slot is a bijection).
 __global__ void kp_blocks_kernel(kp_geom g, const kp_postab *__restrict__ tabs, kp_blockgen bg,
-                                 const uint32_t *__restrict__ brank, const uint64_t *__restrict__ hoff,
-                                 uint32_t *__restrict__ hlist, uint32_t *__restrict__ kpos, uint64_t *__restrict__ hdig,
+                                 const uint32_t *__restrict__ brank, const uint32_t *__restrict__ coff,
+                                 const uint64_t *__restrict__ hoff, uint32_t *__restrict__ hlist, uint32_t *__restrict__ kpos, uint64_t *__restrict__ hdig,
                                  uint64_t *__restrict__ hnp) {
     for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < g.nblocks;
          h += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t hd, hn;
-        const uint64_t q = kp_block_slot(g, tabs, bg, brank, hoff, h, &hd, &hn);
+        const uint64_t q = kp_block_slot(g, tabs, bg, brank, coff, hoff, h, &hd, &hn);
         hlist[q] = (uint32_t)h;
         kpos[h] = (uint32_t)q;
         hdig[q] = hd;
@@ -54,6 +54,17 @@ static kp_blockgen blockgen_of(const kp::host_plan &hp) {
     memset(&bg, 0, sizeof(bg));
     bg.hs = hp.hs;
     for (int j = 0; j < hp.g.kh; ++j) bg.perm[j] = (int8_t)hp.perm[j];
+    bg.nfast = hp.nfast;
+    for (int j = 0; j < hp.nfast; ++j) {  // the class order's level tables of the fast positions
+        const int i = hp.g.t + hp.perm[j];
+        const kp_postab &T = hp.tabs[i];
+        // levels 0 .. n - 1: a position's digits are the non-empty subsets of its code's n
+        // nucleotides, and a digit's level is its subset's size - 1 (kp_plan.h tabs.lev)
+        bg.nlev[j] = (uint8_t)hp.g.n[i];
+        for (uint32_t d = 0; d < hp.g.r[i]; ++d) bg.didx[j][d] = bg.lcnt[j][T.lev[d]]++;
+        for (uint32_t d = 0; d < hp.g.r[i]; ++d)
+            if (T.np[d] > 0 && bg.lcnt[j][T.lev[d]] > 1) bg.share[j] |= (uint8_t)(1u << T.lev[d]);
+    }
     return bg;
 }
 
@@ -141,11 +152,13 @@ static uint32_t node_cap_of(const kp::host_plan &hp) { return (uint32_t)(2 * hp.
 // offsets up, one launch, the small tables freed once it has run.
 static int device_blocks(kp_plan *p) {
     const kp_geom &g = p->hp.g;
-    uint32_t *d_brank = nullptr;
+    uint32_t *d_brank = nullptr, *d_coff = nullptr;
     uint64_t *d_hoff = nullptr;
     int rc;
-    if ((rc = upload(&d_brank, p->hp.brank)) || (rc = upload(&d_hoff, p->hp.hoff))) {
+    if ((rc = upload(&d_brank, p->hp.brank)) || (rc = upload(&d_hoff, p->hp.hoff)) ||
+        (p->hp.nfast > 0 && (rc = upload(&d_coff, p->hp.coff)))) {
         dfree(d_brank);
+        dfree(d_coff);
         dfree(d_hoff);
         return rc;
     }
@@ -156,11 +169,12 @@ static int device_blocks(kp_plan *p) {
     if (he == hipSuccess) {
         const unsigned nb = (unsigned)std::min<uint64_t>((g.nblocks + 255) / 256, 16384);
         hipLaunchKernelGGL(kp_blocks_kernel, dim3(nb), dim3(256), 0, p->ctx->stream, g, p->d_tabs, blockgen_of(p->hp),
-                           d_brank, d_hoff, p->d_hlist, p->d_kpos, p->d_hdig, p->d_hnp);
+                           d_brank, d_coff, d_hoff, p->d_hlist, p->d_kpos, p->d_hdig, p->d_hnp);
         he = hipGetLastError();
         if (he == hipSuccess) he = hipStreamSynchronize(p->ctx->stream);
     }
     dfree(d_brank);
+    dfree(d_coff);
     dfree(d_hoff);
     if (he == hipErrorOutOfMemory)  // the block-list tables do not fit: the lattice is too big here
         return fail(KP_E_NOMEM, "block list of " + p->hp.gp + " (" + std::to_string(g.nblocks) +
@@ -315,13 +329,25 @@ int kp_block_order_check(const char *gen_pat, uint32_t max_block, uint64_t *mism
     std::vector<uint8_t> seen(hp.g.nblocks, 0);
     for (uint64_t h = 0; h < hp.g.nblocks; ++h) {
         uint64_t hd, hn;
-        const uint64_t q = kp_block_slot(hp.g, hp.tabs.data(), bg, hp.brank.data(), hp.hoff.data(), h, &hd, &hn);
+        const uint64_t q = kp_block_slot(hp.g, hp.tabs.data(), bg, hp.brank.data(), hp.coff.data(), hp.hoff.data(), h, &hd, &hn);
         if (q >= hp.g.nblocks || seen[q] || hp.hlist[q] != h || hp.kpos[h] != q || hp.hdig[q] != hd || hp.hnp[q] != hn)
             ++bad;
         else
             seen[q] = 1;
     }
     *mismatches = bad;
+    return KP_OK;
+}
+
+// Host-only (no GPU): the block list of build_plan's host walk, hlist[nblocks] (blocks in
+// list order), and its level offsets hoff[high_levels + 1] (either may be null).
+int kp_block_list_host(const char *gen_pat, uint32_t max_block, uint32_t *hlist, uint64_t *hoff) {
+    if (!gen_pat) return fail(KP_E_ARG, "null argument");
+    kp::host_plan hp;
+    std::string err = kp::build_plan(gen_pat, max_block ? max_block : 4096u, hp, true);
+    if (!err.empty()) return fail(KP_E_ARG, err);
+    if (hlist) memcpy(hlist, hp.hlist.data(), hp.hlist.size() * sizeof(uint32_t));
+    if (hoff) memcpy(hoff, hp.hoff.data(), hp.hoff.size() * sizeof(uint64_t));
     return KP_OK;
 }
 

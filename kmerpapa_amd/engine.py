@@ -130,7 +130,7 @@ EXPORTS = ["kp_last_error", "kp_device_count", "kp_create", "kp_destroy", "kp_de
            "kp_reserve_lanes", "kp_last_pass_stats", "kp_last_launch_ms", "kp_fit_leaves", "kp_dump_lane", "kp_gather_cells", "kp_fold_split",
            "kp_fold_sample", "kp_math_log", "kp_math_libm", "kp_kmer_parse", "kp_kmer_table_info", "kp_kmer_table_copy", "kp_kmer_table_free",
            "kp_format_long_rows", "kp_py_repr", "kp_device_groups", "kp_allkmers_cv", "kp_block_order_check",
-           "kp_plan_block_check", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
+           "kp_plan_block_check", "kp_block_list_host", "kp_greedy", "kp_greedy_leaves", "kp_greedy_host",
            "kp_greedy_last_stats", "kp_apply", "kp_apply_host", "kp_seq_begin", "kp_seq_scan", "kp_seq_sites",
            "kp_seq_end", "kp_seq_last_stats", "kp_seq_host", "kp_pred_begin", "kp_pred_regions", "kp_pred_track",
            "kp_pred_sites", "kp_pred_end", "kp_pred_last_stats", "kp_pred_host", "kp_seq_begin_typed",
@@ -172,6 +172,8 @@ def load():
                                               ctypes.POINTER(KPPlanInfo)]
         L.kp_block_order_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, u64p]
         L.kp_plan_block_check.argtypes = [vp, u64p]
+        if hasattr(L, "kp_block_list_host"):  # (older builds loaded through KMERPAPA_LIB lack it)
+            L.kp_block_list_host.argtypes = [ctypes.c_char_p, ctypes.c_uint32, vp, vp]
         L.kp_kmer_parse.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
                                     ctypes.POINTER(vp)]
         L.kp_kmer_table_info.argtypes = [vp, u64p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
@@ -303,7 +305,7 @@ def _ptr(a):
 
 # launch knobs read by the library (csrc/kp_pass.h, kp_plan.h, kp_plan_dev.h; every setting gives the same scores; they change timing)
 LAUNCH_KNOBS = ("KP_DP_THREADS", "KP_LANES_PER_WG", "KP_XCD_REMAP", "KP_LANE_SPLIT", "KP_NT_STORE", "KP_NT_SLOW",
-                "KP_BLOCK_PERM", "KP_BLOCK_ORDER", "KP_BLOCK_TILE", "KP_LOW_ORDER", "KP_EXACT_LOGS",
+                "KP_BLOCK_PERM", "KP_BLOCK_ORDER", "KP_BLOCK_TILE", "KP_BLOCK_CLASS", "KP_LOW_ORDER", "KP_EXACT_LOGS",
                "KP_CLASS_STREAMS", "KP_NT_SLOW_H", "KP_LDS_BUDGET", "KP_WIDE_SPLIT", "KP_HPD")
 
 
@@ -489,6 +491,18 @@ def block_order_check(gen_pat, max_block=0):
     n = ctypes.c_uint64()
     _check(load().kp_block_order_check(gen_pat.encode(), ctypes.c_uint32(max_block), ctypes.byref(n)))
     return n.value
+
+
+def block_list_host(gen_pat, max_block=0):
+    """The block list of ``gen_pat``'s lattice as the host walks it (kp_block_list_host, host
+    code; the order the block-list knobs in the environment select): ``(hlist, hoff)``, the
+    blocks in list order and the level offsets into that list."""
+    info = KPPlanInfo()
+    _check(load().kp_plan_host(gen_pat.encode(), ctypes.c_uint32(max_block), ctypes.byref(info)))
+    hlist = np.zeros(info.nblocks, dtype=np.uint32)
+    hoff = np.zeros(info.high_levels + 1, dtype=np.uint64)
+    _check(load().kp_block_list_host(gen_pat.encode(), ctypes.c_uint32(max_block), _ptr(hlist), _ptr(hoff)))
+    return hlist, hoff
 
 
 def _group_array(groups):

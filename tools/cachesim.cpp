@@ -12,7 +12,12 @@
 // build: hipcc -O2 -std=c++17 -o tools/cachesim tools/cachesim.cpp   (host code only)
 // usage: tools/cachesim GEN_PAT LANES SCHEDULE [param]
 //   SCHEDULE: plan      = the plan's block list, runs of `param` (default 8) per XCD
-//             square    = fibers over the two fastest high positions kept on one XCD
+//             class     = the same with the plan's class order (kp_plan.h, KP_BLOCK_CLASS=1:
+//                         slabs of the KP_NT_SLOW slowest positions, inside them blocks by
+//                         the digit levels of the fast positions, siblings adjacent);
+//                         KP_NT_SLOW=0 drops the slabs, 2 classes four positions
+//             (every other schedule starts from the plain order, KP_BLOCK_CLASS=0)
+//   KP_NT_POS="a,b,.." = high positions read non-temporally (the product: the slab's)
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -53,13 +58,16 @@ int main(int argc, char **argv) {
         return 2;
     }
     kp::host_plan P;
+    std::string sched = argv[3];
+    setenv("KP_BLOCK_CLASS", sched == "class" ? "1" : "0", 1);
     std::string err = kp::build_plan(argv[1], 4096, P);
     if (!err.empty()) {
         fprintf(stderr, "%s\n", err.c_str());
         return 1;
     }
     const int lanes = atoi(argv[2]);
-    const std::string sched = argv[3];
+    const std::string sched_name = sched;
+    if (sched == "class") sched = "plan";  // the list is in class order; dealt as the plan's
     const int param = argc > 4 ? atoi(argv[4]) : 8;
     const kp_geom &g = P.g;
     const double row_bytes = (double)lanes * g.Bpad * 4;
@@ -296,7 +304,7 @@ int main(int argc, char **argv) {
     printf("{\"gen_pat\": \"%s\", \"lanes\": %d, \"schedule\": \"%s\", \"param\": %d, \"row_bytes\": %.0f, "
            "\"l2_rows\": %zu, \"mall_rows\": %zu, \"reads_GB\": %.1f, \"l2_miss_GB\": %.1f, \"mall_miss_GB\": %.1f, "
            "\"writes_GB\": %.1f, \"l2_hit\": %.4f, \"mall_hit_of_l2miss\": %.4f, \"distinct_children_GB\": %.1f}\n",
-           argv[1], lanes, sched.c_str(), param, row_bytes, l2_rows, mall_rows, reads * row_bytes / GB,
+           argv[1], lanes, sched_name.c_str(), param, row_bytes, l2_rows, mall_rows, reads * row_bytes / GB,
            l2miss * row_bytes / GB, mallmiss * row_bytes / GB, writes * row_bytes / GB,
            1.0 - (double)l2miss / reads, 1.0 - (double)mallmiss / l2miss, distinct * row_bytes / GB);
     return 0;
